@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the anonymize / model.convert() hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" = one `model.convert` over one batch of 32 synthetic 5 s @ 16 kHz utterances per rank, everything on
 the path (YAAPT F0, bottleneck extractor, one-hot, generator), inputs resident in HBM.  Rank 0 prints ONE JSON line
-on stdout: the headline (BASELINE configs[1]: tag hifigan_bn_tdnnf_600h_vq_48_v1).  The other BASELINE configs are
-measured in the same run, before it; their full lines (same schema) go to stderr prefixed `CONFIG_LINE ` and their
-value / roofline / cpu_baseline, condensed, into the headline's `configs` object:
+on stdout: the headline (BASELINE configs[1]: tag hifigan_bn_tdnnf_600h_vq_48_v1).
+
+A plain run measures the headline alone: set-up, W warm-up steps, ONE timed window of exactly K steps
+(`ms_per_step` = that window / K), then the line.  `--dump-outputs DIR` writes what the last timed step's convert()
+returned (the anonymized waveforms, [32, 1, 80001] float32) to DIR/convert_y.npy; the inputs and the seeded weights are
+the same in every run with the same arguments, so two builds can be compared output for output.
+
+`--full` measures everything else as well: the headline becomes the median of `--repeats` windows (default 5) with
+its `roofline` and `cpu_baseline`, and the other BASELINE configs are measured in the same run, before it; their
+full lines (same schema) go to stderr prefixed `CONFIG_LINE ` and their value / roofline / cpu_baseline, condensed,
+into the headline's `configs` object:
 
   N = 1   configs[2] (wav2vec2 tag), configs[3] (wav2vec2 tag + f0-transformation=quant_16_awgn_2), then the
           headline; each with its own `roofline` and `cpu_baseline`.
@@ -17,11 +25,12 @@ value / roofline / cpu_baseline, condensed, into the headline's `configs` object
           launch the ranks are used as they are.  Workload per line = the sharded job of SURVEY §8(d)/(e):
           N x K x 32 utterances, contiguous shards of K x 32 per rank, batches of 32 in index order
           (satools_amd.dist.convert_sharded), ONE all_gather_into_tensor of the [K*32, 1, 80001] shards at the
-          end, inside the timed region.  BASELINE configs[4] (wav2vec2 tag; K = 16 at N = 8 is exactly its 4096
-          utterances) is measured first, then the headline tag through the same code (weak scaling: the per-GPU
-          work is fixed, so the driver's N = 1, 2, 4, 8 values are comparable).
+          end, inside the timed region.  With --full, BASELINE configs[4] (wav2vec2 tag; K = 16 at N = 8 is exactly
+          its 4096 utterances) is measured first, then the headline tag through the same code (weak scaling: the
+          per-GPU work is fixed, so the N = 1, 2, 4, 8 values are comparable).  --dump-outputs writes the last
+          batch of the gathered job.
 
-The CPU leg (`cpu_baseline`, rank 0 at N = 1 only) times the oracle — a port of the reference's PyTorch CPU path —
+The CPU leg (`cpu_baseline`, --full, rank 0 at N = 1 only) times the oracle — a port of the reference's PyTorch CPU path —
 on a bounded sample, at 1 thread (the reference's own setting, satools/satools/hifigan/yaapt.py:27) and at the
 host's physical core count.
 """
@@ -218,7 +227,7 @@ def load(tag, f0_transformation, dev):
 def run_steps(model, dev, rank, steps, warmup, jobs, seed_before_each, repeats=1, status="sync"):
     """N = 1 mode: K independent convert() batches, `jobs` deep in flight on separate HIP streams (the reference's
     jobs_per_compute_device, satools/satools/bin/anonymize:85-93), timed `repeats` times back to back (each window = exactly K steps
-    between two device synchronisations).  Returns (list of window seconds, setup_steps).
+    between two device synchronisations).  Returns (list of window seconds, setup_steps, what the last timed step's convert() returned).
     status "sync" (default): the plain convert() call — YAAPT's status word of the batch (the error path: an utterance without a voiced
     frame) is waited for inside every call; "deferred": convert(..., defer_status=True), the word checked before the same job launches its
     NEXT batch and at the end of the window, as the batch job does (pipeline.process_data).  Measured level in this loop (8.91 / 8.93 /
@@ -269,16 +278,17 @@ def run_steps(model, dev, rank, steps, warmup, jobs, seed_before_each, repeats=1
     windows = []
     chk = os.environ.get("SAT_BENCH_HOSTCHK") == "1"
     host_ms = []
+    y = None
     for _ in range(max(1, repeats)):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
             if chk:
                 h0 = time.perf_counter()
-                step()
+                y = step()
                 host_ms.append(1e3 * (time.perf_counter() - h0))
             else:
-                step()
+                y = step()
         drain()                              # every status of the window is checked inside it
         torch.cuda.synchronize()
         windows.append(time.perf_counter() - t0)
@@ -287,7 +297,7 @@ def run_steps(model, dev, rank, steps, warmup, jobs, seed_before_each, repeats=1
         import gc
         print(f"HOSTCHK steps ({status}): host time per step mean {sum(hs) / len(hs):.2f} ms, median {hs[len(hs) // 2]:.2f}, p90 {hs[int(0.9 * len(hs))]:.2f}, "
               f"max {hs[-1]:.2f}; gc counts {gc.get_count()}, gen2 collections {gc.get_stats()[2]['collections']}", file=sys.stderr, flush=True)
-    return windows, setup_steps
+    return windows, setup_steps, y
 
 
 def run_sharded(model, dev, rank, world, steps, warmup, jobs, seed_before_each, gather="f32", repeats=1, chunk_batches=4, status="sync"):
@@ -297,7 +307,8 @@ def run_sharded(model, dev, rank, world, steps, warmup, jobs, seed_before_each, 
     one all_gather_into_tensor, hidden behind compute; `chunk_batches` = 0: that single collective at the end).
     `gather` = "pcm16": the shards are converted to the int16 PCM the reference writes before the collective (half the
     bytes).  The job is timed `repeats` times (each window: barrier + synchronize on both sides, MAX over ranks).
-    Returns a dict: window seconds, exposed all-gather ms, per-rank compute ms, ranks seen, setup_steps, checks."""
+    Returns a dict: window seconds, exposed all-gather ms, per-rank compute ms, ranks seen, setup_steps, checks, the last batch of the
+    gathered job."""
     import torch
     import torch.distributed as dist
     from satools_amd import dist as sdist
@@ -419,7 +430,8 @@ def run_sharded(model, dev, rank, world, steps, warmup, jobs, seed_before_each, 
     del ref, ref2
     return {"windows": windows, "all_gather_ms": gather_ms, "compute_ms_per_rank": compute_ms, "ranks_seen": ranks_seen, "setup_steps": setup_steps,
             "gathered_equals_shard": ok[0].item() == 0.0, "chunked_equals_single_collective": ok[1].item() == 0.0,
-            "chunks": len(stats.get("chunks", [])), "chunk_batches": chunk_batches, "chunk_issue_wait_ms": chunk_ms}
+            "chunks": len(stats.get("chunks", [])), "chunk_batches": chunk_batches, "chunk_issue_wait_ms": chunk_ms,
+            "last_batch": out[n_items - BATCH:]}
 
 
 def last_dispatch():
@@ -645,9 +657,27 @@ def gen_arithmetic(model):
     return f"f32 (matrix products: {g.precision})", PEAK_F16X3, g.precision
 
 
-def one_config(name, tag, f0_tr, a, dev, rank, world, use_pg, steps, warmup, want_cpu, cpu_args, repeats=1, gen_precision=None, want_roofline=True, status=None):
+def dump_outputs(outdir, arrays):
+    """what the timed path returned, as float32 .npy files in `outdir`, at most 64 MB in all: a larger array keeps a fixed, seeded
+    sample of its rows (leading dimension)"""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    budget = 64 * 2 ** 20 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        row = max(1, t[0].numel() * 4)
+        if t.numel() * 4 > budget:
+            keep = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:max(1, budget // row)].sort().values
+            t = t[keep]
+        np.save(os.path.join(outdir, name + ".npy"), t.numpy())
+
+
+def one_config(name, tag, f0_tr, a, dev, rank, world, use_pg, steps, warmup, want_cpu, cpu_args, repeats=1, gen_precision=None, want_roofline=True, status=None,
+               dump=None):
     """measure one BASELINE config on the loaded device; returns the JSON object (rank 0) or None.  `value` = the MEDIAN of
-    `repeats` timed windows of `steps` steps (median of >= 5 repeats), min / max beside it."""
+    `repeats` timed windows of `steps` steps (median of >= 5 repeats), min / max beside it.  `dump`: a directory that
+    receives what the last timed step computed (dump_outputs), written before anything else runs on the model."""
     model = load(tag, f0_tr, dev)
     if gen_precision:
         model.hifigan.precision = gen_precision
@@ -657,7 +687,7 @@ def one_config(name, tag, f0_tr, a, dev, rank, world, use_pg, steps, warmup, wan
     status = status or a.f0_status
     if use_pg:
         r = run_sharded(model, dev, rank, world, steps, warmup, a.jobs, seed_each, a.gather, repeats, a.gather_chunk, status=status)
-        windows, setup = r["windows"], r["setup_steps"]
+        windows, setup, y = r["windows"], r["setup_steps"], r["last_batch"]
         gb = 2 if a.gather == "pcm16" else 4
         mid = sorted(range(len(windows)), key=lambda i: windows[i])[len(windows) // 2]
         comp = r["compute_ms_per_rank"][mid]
@@ -672,7 +702,10 @@ def one_config(name, tag, f0_tr, a, dev, rank, world, use_pg, steps, warmup, wan
                                + ("issued on a communication stream as the batches complete, inside the timed region; all_gather_ms = what is left "
                                   "exposed behind the slowest rank's last batch" if r["chunk_batches"] else "at the end, inside the timed region")}
     else:
-        windows, setup = run_steps(model, dev, rank, steps, warmup, a.jobs, seed_each, repeats, status=status)
+        windows, setup, y = run_steps(model, dev, rank, steps, warmup, a.jobs, seed_each, repeats, status=status)
+    if dump and rank == 0:
+        dump_outputs(dump, {"convert_y": y})
+    del y
     ext = model.bn_extractor
     tie = dict(ext.__dict__.get("tie_stats") or {})
     if rank != 0:
@@ -778,6 +811,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other BASELINE configs, roofline legs, the CPU baseline, "
+                         "the auxiliary forwards, and the headline as the median of --repeats windows (default: the headline alone, "
+                         "one window of --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's convert() returned to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true", help="skip the lines of the other BASELINE configs")
     ap.add_argument("--jobs", type=int, default=4,
@@ -785,8 +824,9 @@ def main():
                          "jobs_per_compute_device, satools/satools/bin/anonymize:85-93)")
     ap.add_argument("--gather", choices=("f32", "pcm16"), default="f32",
                     help="sharded mode: gather the waveforms as f32 (default) or as the int16 PCM the reference writes (half the bytes)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed windows of --steps steps each; `value` = the median window (SURVEY 8(d): median of >= 5 repeats)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed windows of --steps steps each; `value` = the median window (SURVEY 8(d): median of >= 5 repeats); "
+                         "default 5 with --full, else 1")
     ap.add_argument("--gather-chunk", type=int, default=4,
                     help="sharded mode: the waveform exchange is issued in chunks of this many batches on a communication stream while "
                          "the shard is still being computed (0 = one all_gather_into_tensor at the end)")
@@ -804,7 +844,7 @@ def main():
     ap.add_argument("--f0-transformation", default="", help="with --tag: e.g. quant_16_awgn_2")
     a = ap.parse_args()
     a.jobs = max(1, a.jobs)
-    a.repeats = max(1, a.repeats)
+    a.repeats = max(1, a.repeats if a.repeats is not None else (5 if a.full else 1))
     if a.cpu_worker:
         return cpu_worker(a.cpu_worker[0], a.cpu_worker[1], int(a.cpu_worker[2]), int(a.cpu_worker[3]))
 
@@ -817,12 +857,12 @@ def main():
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.exit(subprocess.call(cmd, env=env))
 
-    # N = 1, default run: every config but the headline is measured in its OWN process, one after the other, BEFORE this process touches
+    # N = 1, --full run: every config but the headline is measured in its OWN process, one after the other, BEFORE this process touches
     # the GPU (round 6: in one process the later configs of a run were slower than the same config alone — per-step host waits with a
     # heavier tail, and a device-wide slowdown for the rest of the process once a high-priority stream had been created, DESIGN toolchain
     # note 22 — so a line must not depend on what ran before it).  The children print their full line; the headline runs here, last.
     child_lines = []
-    side_in_children = (a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.tag and not a.headline_only and not a.child_config and
+    side_in_children = (a.full and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.tag and not a.headline_only and not a.child_config and
                         os.environ.get("SAT_BENCH_FORCE_PG") != "1" and os.environ.get("SAT_BENCH_DRYRUN") != "1")
     if side_in_children:
         k2 = min(a.steps, 12)
@@ -846,7 +886,7 @@ def main():
         for spec in specs:
             spec["repeats"] = min(a.repeats, 3)
             child_env = dict(os.environ, **spec.pop("env", {}))
-            cmd = [sys.executable, os.path.abspath(__file__), "--child-config", json.dumps(spec), "--jobs", str(a.jobs), "--f0-status", a.f0_status,
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--child-config", json.dumps(spec), "--jobs", str(a.jobs), "--f0-status", a.f0_status,
                    "--gather", a.gather] + (["--no-cpu-baseline"] if a.no_cpu_baseline else []) + (["--gen-precision", a.gen_precision] if a.gen_precision else [])
             # (a side config that fails or hangs must not take the headline with it: it is reported on stderr and left out of `configs`)
             try:
@@ -886,7 +926,7 @@ def main():
         torch.cuda.synchronize()
         flush_c_stdio()
 
-    want_cpu = (not a.no_cpu_baseline) and world == 1 and not use_pg
+    want_cpu = a.full and (not a.no_cpu_baseline) and world == 1 and not use_pg
     lines = list(child_lines)
     if a.child_config:
         # one side config, alone in this process: its full line on stdout
@@ -901,7 +941,7 @@ def main():
         plan = [("--tag", a.tag, a.f0_transformation, a.steps, a.warmup, dict(n_utt=8, runs_1=1, runs_n=3, n_utt_1=4))]
     elif use_pg:
         k2 = min(a.steps, 16)
-        plan = ([] if a.headline_only else [("configs[4]", TAG_W2V2, "", k2, min(a.warmup, 4), None)]) + \
+        plan = ([] if a.headline_only or not a.full else [("configs[4]", TAG_W2V2, "", k2, min(a.warmup, 4), None)]) + \
                [("configs[1] sharded", TAG, "", a.steps, a.warmup, None)]
     else:
         # (the other configs of a default N = 1 run were measured in child processes above)
@@ -909,7 +949,8 @@ def main():
     for i, (name, tag, f0_tr, steps, warmup, cpu_args) in enumerate(plan):
         headline = i == len(plan) - 1
         out = one_config(name, tag, f0_tr, a, dev, rank, world, use_pg, steps, warmup, want_cpu and cpu_args is not None, cpu_args or {},
-                         repeats=a.repeats if headline else min(a.repeats, 3), gen_precision=a.gen_precision)
+                         repeats=a.repeats if headline else min(a.repeats, 3), gen_precision=a.gen_precision, want_roofline=a.full,
+                         dump=a.dump_outputs if headline else None)
         torch.cuda.empty_cache()
         if rank == 0:
             lines.append(out)

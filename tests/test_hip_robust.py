@@ -390,11 +390,11 @@ def test_sharded_job_runs_on_rccl_in_a_child_process():
     re-executed): the ranks RCCL saw, the gathered job = the shard, both tags, float and PCM16 gathers"""
     env = dict(os.environ, SAT_BENCH_FORCE_PG="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    # (--headline-only: the fbank tag of configs[1]; without it the wav2vec2 tag of BASELINE configs[4] runs first through the same
-    # code and its line goes to stderr as CONFIG_LINE)
+    # (--headline-only: the fbank tag of configs[1]; with --full and without it the wav2vec2 tag of BASELINE configs[4] runs first
+    # through the same code and its line goes to stderr as CONFIG_LINE)
     # (round 5: the exchange is issued in chunks of --gather-chunk batches on a communication stream while the shard is computed;
     # 0 = the single all_gather_into_tensor at the end, which every run also performs afterwards as the checked reference)
-    for extra in (["--headline-only", "--gather-chunk", "1"], ["--gather", "pcm16"], ["--headline-only", "--gather-chunk", "0"]):
+    for extra in (["--headline-only", "--gather-chunk", "1"], ["--full", "--gather", "pcm16"], ["--headline-only", "--gather-chunk", "0"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
                             "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -414,6 +414,25 @@ def test_sharded_job_runs_on_rccl_in_a_child_process():
             assert cfg["utterances"] == 64 and line["n_gpus"] == 1 and line["value"] > 0 and line["repeats"]["windows"] >= 1
         if len(lines) == 2:
             assert "wav2vec2" in lines[1]["config"]["workload"] and "wav2vec2" not in lines[0]["config"]["workload"]
+
+
+def test_plain_bench_times_exactly_its_steps_and_dumps_the_last_step(tmp_path):
+    """a plain `bench.py` run (no --full): the headline alone in ONE window of exactly --steps steps, no side measurements, and
+    --dump-outputs writes the last timed step's convert() output as float32; a second run with the same arguments writes the same"""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["repeats"]["windows"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "roofline" not in line and "cpu_baseline" not in line and "configs" not in line
+        assert "CONFIG_LINE" not in r.stderr
+        y = np.load(out / "convert_y.npy")
+        assert y.dtype == np.float32 and y.shape == (32, 1, 80001) and np.isfinite(y).all() and np.abs(y).max() > 0
+        dumps.append(y)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 @pytest.mark.parametrize("tag", [FBANK_TAG, W2V2_TAG])

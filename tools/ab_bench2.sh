@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
 run() {
   local label=$1; shift
-  env "$@" python3 bench.py --headline-only --no-cpu-baseline 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --headline-only --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$label', d['value'], d['ms_per_step'])"
 }
 run "default            "

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
 run() {
   local label=$1; local jobs=$2; shift; shift
-  env "$@" python3 bench.py --headline-only --no-cpu-baseline --jobs $jobs 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --headline-only --no-cpu-baseline --jobs $jobs 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$label jobs $jobs', d['value'], d['ms_per_step'])"
 }
 for rep in 1 2; do

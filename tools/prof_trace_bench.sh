@@ -6,7 +6,7 @@ TAG=${1:-r04t}; shift || true
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd $R
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --headline-only --no-cpu-baseline --steps 24 "$@" > $O/bench_line.json 2> $O/bench.err
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --full --headline-only --no-cpu-baseline --steps 24 "$@" > $O/bench_line.json 2> $O/bench.err
 T=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 $R/tools/trace_timeline.py $T > $R/gpurun_out/${TAG}_bench_timeline.txt
 python3 $R/tools/trace_forward.py $T f0_stats_kernel 20 > $R/gpurun_out/${TAG}_bench_one_step.txt
