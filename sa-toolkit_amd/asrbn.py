@@ -150,6 +150,11 @@ class TieFix:
             return False
         ext = self.ext
         rows = self.status.rows()
+        if rows and not ext._exact_stored():
+            # a frozen model without the exact-f32 packings: the flagged utterances keep the configured arithmetic's indices, counted
+            st = ext.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
+            st["unguarded"] = st.get("unguarded", 0) + len(rows)
+            rows = []
         if not rows:
             self.stage, self.hit = 2, []
             self._drop()
@@ -249,8 +254,9 @@ class _TdnnfBase(nn.Module):
     #: near-tie guard of the VQ decision (chain/nn.py:424-459 is INDEX work: the bar is exact).  In split-f16 arithmetic a frame whose
     #: two best codes lie closer than this many standard deviations of the arithmetic's own (calibrated) feature error is counted
     #: on the device, and its utterance is decided again on the exact-f32 kernels — so the default arithmetic returns the exact
-    #: kernels' indices (536-utterance sweep per tag: tests/test_hip_robust.py).  0 switches the guard off; frozen models (no f32
-    #: parameters to fall back on) run without it.
+    #: kernels' indices (536-utterance sweep per tag: tests/test_hip_robust.py).  0 switches the guard off.  A frozen model runs it
+    #: on the calibration and the exact-f32 packings its file stores; without the latter (wav2vec2 tag, default export) flagged
+    #: utterances are only counted (`tie_stats["unguarded"]`).
     vq_tie_sigmas = float(os.environ.get("SATOOLS_AMD_VQ_TIE_SIGMAS", "4"))
 
     def _init_cache(self):
@@ -302,7 +308,13 @@ class _TdnnfBase(nn.Module):
         return c
 
     def _prepare(self, device):
-        if self.__dict__.get("_frozen"):           # caches installed by frozen.load_frozen
+        if self.__dict__.get("_frozen"):           # caches installed by frozen.load_frozen: one per precision the file stores
+            hit = self.__dict__.get("_cache_store", {}).get(self.precision)
+            if hit is None:
+                raise _lib.SatError(f"frozen model: its file stores no {self.precision!r} packing of the TDNNF stack "
+                                    "(export_frozen stores the configured one and the exact-f32 one; on the wav2vec2 tag the latter only with "
+                                    "exact_extractor=True)")
+            self._cache_key, self._cache, self._cache_full = hit
             return
         key = (self.precision,) + self._param_key()
         if self._cache_key == key:
@@ -498,11 +510,25 @@ class _TdnnfBase(nn.Module):
 
     def _tie_guard(self, device):
         """-> (pair distances of the codebook [n, n], tie_scale) for sat_vq_argmin_gather_tie_f32, or None when the guard is off.
-        tie_scale = 2 K sigma_rel / sqrt(D): sigma_rel = |z - z_exact| / |z_exact| of this extractor's split-f16 arithmetic against its
-        exact-f32 twin on two synthetic 2 s utterances, measured once per (weights, precision) — the error of d[a] - d[a'] is
-        2 dz . (e_a' - e_a), i.e. ~ N(0, (2 sigma_c |e_a - e_a'|)^2) with sigma_c = sigma_rel |z_t| / sqrt(D) per component."""
-        if not self.vq_tie_sigmas or self.__dict__.get("_frozen") or self.__dict__.get("_tie_busy"):
+        tie_scale = 2 K sigma_rel / sqrt(D) with K = vq_tie_sigmas (`_tie_calibration`) — the error of d[a] - d[a'] is 2 dz . (e_a' - e_a),
+        i.e. ~ N(0, (2 sigma_c |e_a - e_a'|)^2) with sigma_c = sigma_rel |z_t| / sqrt(D) per component."""
+        if not self.vq_tie_sigmas or self.__dict__.get("_tie_busy"):
             return None
+        if all(getattr(self, k) == "f32" for k in self._precision_keys()):
+            return None
+        cal = self._tie_calibration(device)
+        if cal is None:
+            return None
+        pair, sigma_rel, D = cal
+        return pair, 2.0 * self.vq_tie_sigmas * sigma_rel / math.sqrt(D)
+
+    def _tie_calibration(self, device):
+        """-> (pair distances of the codebook [n, n] f32, sigma_rel, D) of the configured arithmetic, or None where it is exact f32.
+        sigma_rel = |z - z_exact| / |z_exact| of this extractor's split-f16 arithmetic against its exact-f32 twin on two synthetic 2 s
+        utterances, measured once per (weights, precision).  A frozen model has no parameters to measure with: it returns what its
+        file stores (measured on the full model at export time, frozen.export_frozen)."""
+        if self.__dict__.get("_frozen"):
+            return self.__dict__.get("_tie_frozen")
         if all(getattr(self, k) == "f32" for k in self._precision_keys()):
             return None
         key = tuple(getattr(self, k) for k in self._precision_keys()) + self._param_key() + (str(device),)
@@ -522,8 +548,12 @@ class _TdnnfBase(nn.Module):
             finally:
                 self.__dict__["_tie_busy"] = False
             g = self.__dict__["_tie"] = (key, pair, sigma_rel, z.shape[1])
-        _, pair, sigma_rel, D = g
-        return pair, 2.0 * self.vq_tie_sigmas * sigma_rel / math.sqrt(D)
+        return g[1:]
+
+    def _exact_stored(self):
+        """can the exact-f32 kernels run (the second decision of near-tie utterances)?  Always, unless a frozen model's file holds
+        no exact-f32 packing"""
+        return not self.__dict__.get("_frozen") or "f32" in self.__dict__.get("_cache_store", {})
 
     def _run_stack_guarded(self, feats, want_aux=False):
         """`_run_stack` with the near-tie count: -> (result, TieStatus or None)"""
@@ -582,6 +612,8 @@ class _TdnnfBase(nn.Module):
     def _prepare_full(self, device):
         self._prepare(device)
         if self._cache_full is None:
+            if self.__dict__.get("_frozen"):
+                raise _lib.SatError(f"frozen model: the ASR head is stored in the exported arithmetic only, not in {self.precision!r}")
             split = self.precision == "f16x3"
             f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
             after = [m for m in self.tdnnfs_after if isinstance(m, TDNNFBatchNormParams)]

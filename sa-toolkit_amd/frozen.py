@@ -9,14 +9,19 @@ utt2spk).  `load_frozen(path, device)` rebuilds the same `Net` object WITHOUT pa
 placeholders: a frozen model is inference-only, like `final.jit`) and installs the packed weights directly: no fold, no
 pack, no 1.3 GB of f32 weights of the wav2vec2 tag on the device.  The public interface (convert / get_bn / get_f0 /
 extract_features / _forward / spk / ...) is unchanged and the outputs are bit-identical to the model the file was made
-from (tests/test_hip_robust.py)."""
+from (tests/test_hip_robust.py).
+
+The VQ near-tie guard (asrbn._TdnnfBase.vq_tie_sigmas) travels with the file: its calibration (sigma_rel, the codebook's pair
+distances, D), measured on the full model at export time, and the exact-f32 packing of the TDNNF stack that decides flagged
+utterances again.  The wav2vec2 tag's exact-f32 encoder (~1.2 GB) is stored only with `exact_extractor=True`; without it a
+frozen wav2vec2 model still counts its near-ties but delivers them undecided (`tie_stats["unguarded"]`, one warning at load)."""
 import torch
 import torch.nn as nn
 
 from . import _lib
 
-FORMAT = "satools_amd.frozen/2"      # 2: plain build arguments only, SAT_CONV_F16F8R second packings
-OLD_FORMATS = ("satools_amd.frozen/1",)
+FORMAT = "satools_amd.frozen/3"      # 3: near-tie guard calibration + exact-f32 extractor packings
+OLD_FORMATS = ("satools_amd.frozen/1", "satools_amd.frozen/2")
 
 
 def _enc(x):
@@ -93,8 +98,10 @@ def _strip_parameters(net, device):
                 m._buffers[k] = torch.empty(0, device=device)
 
 
-def export_frozen(model, path):
-    """model: an anonymizer `Net` on the HIP device (satools_amd.load_model(...).to('cuda'))"""
+def export_frozen(model, path, exact_extractor=False):
+    """model: an anonymizer `Net` on the HIP device (satools_amd.load_model(...).to('cuda')).  Besides the configured packings the
+    file holds the near-tie guard's calibration and the exact-f32 packings that decide flagged utterances again: the TDNNF stack's
+    always (~24 MB), the wav2vec2 encoder's (~1.2 GB) only with `exact_extractor=True`."""
     gen = model.hifigan
     dev = model._device()
     if dev.type != "cuda":
@@ -102,6 +109,8 @@ def export_frozen(model, path):
     if gen.__dict__.get("_frozen"):
         raise _lib.SatError("export_frozen: the model is already a frozen one")
     ext = model.bn_extractor
+    # (the calibration runs the extractor in both arithmetics: before the configured packings are taken)
+    cal = ext._tie_calibration(dev)
     gen._prepare(dev)
     ext._prepare(dev)
     blob = {"format": FORMAT, "kind": "anonymizer",
@@ -112,7 +121,9 @@ def export_frozen(model, path):
                           # second packings of the thick stages' ResBlock convs for SAT_CONV_F16F8R ("f16f8r"), {conv id: tensor}
                           "packed8": _enc({str(k): v for k, v in (gen.__dict__.get("_packed8") or {}).items()}),
                           "f8_stages": int(gen.f8_stages)},
-            "extractor": {"class": type(ext).__name__, "precision": ext.precision, "cache": _enc(ext._cache)}}
+            "extractor": {"class": type(ext).__name__, "precision": ext.precision, "cache": _enc(ext._cache),
+                          # near-tie guard of the VQ decision (asrbn._TdnnfBase._tie_calibration); None: the arithmetic is exact f32
+                          "tie": None if cal is None else {"pair": _enc(cal[0]), "sigma_rel": float(cal[1]), "D": int(cal[2])}}}
     if hasattr(ext, "_prepare_full"):
         full = ext._prepare_full(dev)
         blob["extractor"]["cache_full"] = _enc({"after": [c for _, c in full["after"]], "prefinal": [c for _, c in full["prefinal"]],
@@ -121,6 +132,21 @@ def export_frozen(model, path):
         blob["extractor"]["w2"] = _enc(ext._prepare_w2v2(dev))
         blob["extractor"]["mm_mode"] = int(ext._mm_mode)
         blob["extractor"]["w2v2_precision"] = ext.w2v2_precision
+    # the exact-f32 packings of what is not configured as exact f32 (the wav2vec2 encoder's on request only)
+    need = [k for k in ext._precision_keys() if getattr(ext, k) != "f32"]
+    if need and (exact_extractor or "w2v2_precision" not in need):
+        exact = {}
+        with ext._exact(ext):
+            if "precision" in need:
+                ext._prepare(dev)
+                exact["cache"] = _enc(ext._cache)
+            if "w2v2_precision" in need:
+                exact["w2"] = _enc(ext._prepare_w2v2(dev))
+                exact["mm_mode"] = int(ext._mm_mode)
+        ext._prepare(dev)                           # the configured packings current again
+        if hasattr(ext, "_prepare_w2v2"):
+            ext._prepare_w2v2(dev)
+        blob["extractor"]["exact"] = exact
     torch.cuda.synchronize(dev)
     torch.save(blob, path)
     return path
@@ -161,16 +187,34 @@ def load_frozen(path, device="cuda"):
         raise _lib.SatError(f"{path}: extractor {e['class']} does not match the configuration ({type(ext).__name__})")
     ext.precision = e["precision"]
     ext._cache = _dec(e["cache"], device)
+    ext._cache_full = None
     if "cache_full" in e:
         cf = _dec(e["cache_full"], device)
         after = [m for m in ext.tdnnfs_after if isinstance(m, TDNNFBatchNormParams)]
         ext._cache_full = {"after": list(zip(after, cf["after"])),
                            "prefinal": list(zip((ext.prefinal_chain, ext.prefinal_xent), cf["prefinal"])), "out": cf["out"]}
+    # one entry per stored precision (asrbn._TdnnfBase._prepare picks by the current one: `_exact(...)` runs the exact-f32 packing)
+    ex = e.get("exact") or {}
+    ext._cache_key = (ext.precision,)
+    store = ext.__dict__["_cache_store"] = {ext.precision: (ext._cache_key, ext._cache, ext._cache_full)}
+    if "cache" in ex:
+        store["f32"] = (("f32",), _dec(ex["cache"], device), None)
     if "w2" in e:
         ext._w2 = _dec(e["w2"], device)
         ext._mm_mode = e["mm_mode"]
         ext.w2v2_precision = e["w2v2_precision"]
+        ext._w2_key = (ext.w2v2_precision,)
+        w2s = ext.__dict__["_w2_store"] = {ext.w2v2_precision: (ext._w2_key, ext._w2, ext._mm_mode)}
+        if "w2" in ex:
+            w2s["f32"] = (("f32",), _dec(ex["w2"], device), int(ex["mm_mode"]))
+    tie = e["tie"]
+    ext.__dict__["_tie_frozen"] = None if tie is None else (_dec(tie["pair"], device), float(tie["sigma_rel"]), int(tie["D"]))
     ext.__dict__["_frozen"] = True
+    if tie is not None and not ext._exact_stored():
+        import logging
+        logging.getLogger("satools_amd").warning(
+            "%s: no exact-f32 packing of the extractor stored: near-tie VQ decisions will not be decided again (counted in "
+            "bn_extractor.tie_stats['unguarded']); export_frozen(..., exact_extractor=True) stores it", path)
     torch.cuda.synchronize(device)
     net.eval()
     return net

@@ -165,7 +165,12 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
     fe_wrapped_gemm = int(os.environ.get("SATOOLS_AMD_W2V2_FE_WRAPPED_GEMM", "1"))
 
     def _prepare_w2v2(self, device):
-        if self.__dict__.get("_frozen"):           # caches installed by frozen.load_frozen
+        if self.__dict__.get("_frozen"):           # packings installed by frozen.load_frozen: one per precision the file stores
+            hit = self.__dict__.get("_w2_store", {}).get(self.w2v2_precision)
+            if hit is None:
+                raise _lib.SatError(f"frozen model: its file stores no {self.w2v2_precision!r} packing of the wav2vec2 encoder "
+                                    "(export_frozen(..., exact_extractor=True) stores the exact-f32 one)")
+            self._w2_key, self._w2, self._mm_mode = hit
             return self._w2
         key = (self.w2v2_precision,) + tuple((p.data_ptr(), p._version, str(p.device)) for p in self.preprocessor.parameters())
         if self._w2_key == key:
@@ -384,6 +389,9 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
 
     def _features_of(self, x):
         return self.features(x)
+
+    def _exact_stored(self):
+        return super()._exact_stored() and (not self.__dict__.get("_frozen") or "f32" in self.__dict__.get("_w2_store", {}))
 
     def _exact_rows(self, rows, feats, wav, spans=None):
         """flagged utterances again on the exact-f32 kernels: the encoder is recomputed for those rows; their frames and their own

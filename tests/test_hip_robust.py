@@ -463,6 +463,126 @@ def test_frozen_export_round_trip(tmp_path, tag):
     assert os.path.getsize(path) < (1.5e9 if "wav2vec2" in tag else 2.0e8)
 
 
+def _convert_forced_window(model, wav, tg):
+    """convert() with the near-tie guard forced to flag and rewrite every utterance (as test_hip_guards.py
+    test_convert_patches_near_tie_utterances) -> (y, tie_stats of that call, y of the deferred form, its rewritten rows)"""
+    ext = model.bn_extractor
+    keep = ext.vq_tie_sigmas
+    ext.vq_tie_sigmas, ext.vq_tie_force_patch = 1e6, True
+    ext.__dict__.pop("tie_stats", None)
+    try:
+        y = model.convert(wav, target=tg).clone()
+        stats = dict(ext.tie_stats)
+        y_def, st = model.convert(wav, target=tg, defer_status=True)
+        st.check()
+        torch.cuda.synchronize()
+        return y, stats, y_def.clone(), st.rows
+    finally:
+        ext.vq_tie_sigmas, ext.vq_tie_force_patch = keep, False
+
+
+# 5 s `harm` batches of test_vq_flip_rate_of_the_default_arithmetic whose utterances 3005 (first batch) and 3260, 3274, 3278 (second)
+# carry near-ties the fbank tag's default window flags
+FROZEN_TIE_BATCHES = (3000, 3256)
+
+
+def test_frozen_fbank_model_keeps_the_near_tie_guard(tmp_path):
+    """A frozen fbank-tag model decides near-tie utterances again like the model it was exported from: the file stores the guard's
+    calibration and the exact-f32 packing of the TDNNF stack.  (1) Forced window (every utterance flagged and rewritten): 3 utterances
+    decided again, the bits of the unfrozen model's convert(), plain and deferred.  (2) The default window on two 32 x 5 s batches
+    (seeds 3000-3031 and 3256-3287: FROZEN_TIE_BATCHES) that carry flagged utterances: the delivered indices are the exact-f32
+    kernels' and as many utterances are decided again as on the unfrozen model."""
+    import satools_amd
+    from satools_amd import synthetic
+    model = satools_amd.load_model("synthetic:" + FBANK_TAG)
+    model.to(DEV)
+    model.eval()
+    ext = model.bn_extractor
+    wav = synthetic.harm_batch([31, 32, 33], 32000).to(DEV)
+    tg = [model.spk[1], model.spk[0], model.spk[2]]
+    y_ref, st_ref, _, _ = _convert_forced_window(model, wav, tg)
+    assert st_ref["rerun"] == 3, st_ref
+    batches = [synthetic.harm_batch(list(range(s, s + 32)), 80000).to(DEV) for s in FROZEN_TIE_BATCHES]
+    exact, rerun_ref = [], []
+    for w in batches:
+        with ext._exact(ext):
+            _, (_, idx32, _) = ext.extract_bn(w.clone(), want_aux=True)
+        exact.append(idx32.clone())
+        ext.__dict__.pop("tie_stats", None)
+        idx, _ = ext.vq_indices(w)
+        assert torch.equal(idx, idx32)
+        rerun_ref.append(ext.tie_stats["rerun"])
+    assert sum(rerun_ref) >= 1, rerun_ref          # the set carries near-ties: otherwise this part proves nothing
+    path = str(tmp_path / "final.frozen")
+    satools_amd.export_frozen(model, path)
+    del model, ext
+    torch.cuda.empty_cache()
+    fz = satools_amd.load_frozen(path, DEV)
+    fe = fz.bn_extractor
+    y, st, y_def, rows = _convert_forced_window(fz, wav, tg)
+    print(f"frozen fbank model, forced window: {st}; default window: {rerun_ref} utterances decided again on the unfrozen model")
+    assert st["rerun"] == 3 and st.get("unguarded", 0) == 0, st
+    assert torch.equal(y, y_ref)
+    assert rows == [0, 1, 2] and torch.equal(y_def, y)
+    for w, idx32, n_ref in zip(batches, exact, rerun_ref):
+        fe.__dict__.pop("tie_stats", None)
+        idx, _ = fe.vq_indices(w)
+        assert fe.tie_stats["rerun"] == n_ref, (fe.tie_stats, n_ref)
+        assert torch.equal(idx, idx32)
+    with fe._exact(fe):                             # the exact-f32 packing really runs under _exact (not the split one again)
+        _, (_, idx32_f, _) = fe.extract_bn(batches[0].clone(), want_aux=True)
+    assert torch.equal(idx32_f, exact[0])
+
+
+def test_frozen_wav2vec2_model_guard_with_and_without_the_exact_encoder(tmp_path, caplog):
+    """wav2vec2 tag.  Default export (the exact-f32 encoder, ~1.2 GB, left out; the file stays under the 1.5e9 bytes of
+    test_frozen_export_round_trip): one warning at load, near-ties still counted — under the forced window every utterance is
+    `unguarded`, none decided again — and convert() runs; asking for the exact kernels raises instead of running the split packing.
+    Opt-in export (`exact_extractor=True`): the forced window decides all 3 utterances again, to the unfrozen model's bits."""
+    import logging
+
+    import satools_amd
+    from satools_amd import _lib, synthetic
+    model = satools_amd.load_model("synthetic:" + W2V2_TAG)
+    model.to(DEV)
+    model.eval()
+    wav = synthetic.harm_batch([31, 32, 33], 32000).to(DEV)
+    tg = [model.spk[1], model.spk[0], model.spk[2]]
+    y_ref, st_ref, _, _ = _convert_forced_window(model, wav, tg)
+    assert st_ref["rerun"] == 3, st_ref
+    p0, p1 = str(tmp_path / "default.frozen"), str(tmp_path / "exact.frozen")
+    satools_amd.export_frozen(model, p0)
+    satools_amd.export_frozen(model, p1, exact_extractor=True)
+    s0, s1 = os.path.getsize(p0), os.path.getsize(p1)
+    print(f"frozen wav2vec2 files: default {s0 / 1e9:.3f} GB, with the exact-f32 extractor {s1 / 1e9:.3f} GB")
+    assert s0 < 1.5e9 < s1
+    del model
+    torch.cuda.empty_cache()
+
+    with caplog.at_level(logging.WARNING, logger="satools_amd"):
+        fz = satools_amd.load_frozen(p0, DEV)
+    warned = [r for r in caplog.records if "near-tie" in r.getMessage()]
+    assert len(warned) == 1, [r.getMessage() for r in caplog.records]
+    fe = fz.bn_extractor
+    y, st, _, rows = _convert_forced_window(fz, wav, tg)
+    assert st["unguarded"] == 3 and st["rerun"] == 0 and st["utterances"] == 3, st
+    assert rows == [] and y.shape == y_ref.shape and torch.isfinite(y).all()
+    with pytest.raises(_lib.SatError):
+        with fe._exact(fe):
+            fe.extract_bn(wav.clone(), want_aux=True)
+    del fz, fe
+    torch.cuda.empty_cache()
+
+    caplog.clear()
+    with caplog.at_level(logging.WARNING, logger="satools_amd"):
+        fz = satools_amd.load_frozen(p1, DEV)
+    assert not [r for r in caplog.records if "near-tie" in r.getMessage()]
+    y, st, y_def, rows = _convert_forced_window(fz, wav, tg)
+    assert st["rerun"] == 3 and st.get("unguarded", 0) == 0, st
+    assert torch.equal(y, y_ref)
+    assert rows == [0, 1, 2] and torch.equal(y_def, y)
+
+
 def test_check_precision_guards_against_out_of_range_checkpoints():
     """Net.check_precision(): the load-time guard of the split-f16 arithmetic.  A sane checkpoint passes and keeps its
     kernels; one whose inner activations exceed the f16 range (conv1 of every ResBlock step scaled by 2^18 against its

@@ -473,3 +473,19 @@ def test_ragged_yaapt_length_dims_are_the_plans():
             q = f0.make_plan(n, dict(opts))
             assert f0.length_dims(P, n) == [q.n, q.L, q.nframes, q.tda_nframes], (opts, n)
             assert (q.pad, q.frame_jump, q.frame_size, q.tda_len) == (P.pad, P.frame_jump, P.frame_size, P.tda_len)
+
+
+def test_frozen_files_of_older_formats_are_refused(tmp_path):
+    """a frozen file of format /2 (written before the near-tie guard's calibration and exact-f32 packings travelled with it) or /1
+    is refused with the re-export message before anything is built, and a file of the current format is named"""
+    from satools_amd import frozen
+    assert frozen.FORMAT == "satools_amd.frozen/3"
+    for old in ("satools_amd.frozen/2", "satools_amd.frozen/1"):
+        path = str(tmp_path / (old[-1] + ".frozen"))
+        torch.save({"format": old, "kind": "anonymizer", "extractor": {}}, path)
+        with pytest.raises(_lib.SatError, match="re-export"):
+            frozen.load_frozen(path, "cpu")
+    path = str(tmp_path / "other.frozen")
+    torch.save({"format": "something else"}, path)
+    with pytest.raises(_lib.SatError, match="not a satools_amd.frozen/3"):
+        frozen.load_frozen(path, "cpu")
