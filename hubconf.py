@@ -33,12 +33,20 @@ def _load(tag_version):
 
 
 def asr_bn_extractor(tag_version="bn_tdnnf_wav2vec2_vq_48_v1", exit_if_new_version=False):
-    """ASR-bottleneck extractor (`extract_bn`); returned in eval mode like the reference"""
+    """ASR-bottleneck extractor (`extract_bn`); returned in eval mode like the reference.
+
+    tag_version: one of 'bn_tdnnf_wav2vec2_vq_48_v1', 'bn_tdnnf_wav2vec2_100h_aug_v1', 'bn_tdnnf_600h_aug_v1',
+    'bn_tdnnf_600h_vq_48_v1', 'bn_tdnnf_100h_vq_64_v1', 'bn_tdnnf_100h_vq_256_v1', 'bn_tdnnf_100h_aug_v1'
+    (the `*_aug` tags have no VQ bottleneck: `extract_bn` returns the 256-dim bottleneck itself)"""
     m = _load(tag_version)
     m.eval()
     return m
 
 
 def anonymization(tag_version="hifigan_bn_tdnnf_wav2vec2_vq_48_v1", exit_if_new_version=False):
-    """anonymization model (`convert`, `get_bn`, `get_f0`, ...)"""
+    """anonymization model (`convert`, `get_bn`, `get_f0`, ...).
+
+    tag_version: one of 'hifigan_bn_tdnnf_wav2vec2_vq_48_v1', 'hifigan_bn_tdnnf_wav2vec2_100h_aug_v1',
+    'hifigan_bn_tdnnf_600h_aug_v1', 'hifigan_bn_tdnnf_600h_vq_48_v1', 'hifigan_bn_tdnnf_100h_vq_64_v1',
+    'hifigan_bn_tdnnf_100h_vq_256_v1', 'hifigan_bn_tdnnf_100h_aug_v1'"""
     return _load(tag_version)

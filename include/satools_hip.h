@@ -409,6 +409,16 @@ int sat_vq_argmin_gather_f32(const float* z, const float* codebook, float* q, in
 int sat_vq_argmin_gather_tie_f32(const float* z, const float* codebook, float* q, int32_t* idx, float* dist,
                                  const float* pair_dist, float tie_scale, int32_t* tie_count,
                                  int B, int D, int T, int n_codes, void* stream);
+/* The same two operations (VectorQuantizerEMA.forward eval branch, chain/nn.py:402-476) for codebooks that do not fit LDS whole:
+ * the codebook is walked in tiles of 64 codes staged through LDS, best and runner-up carried across the tiles.  Arguments, formula,
+ * chain order, first-minimum rule and the near-tie rule as above; for n_codes <= 64 the results have the bits of the pair above.
+ * 1 <= n_codes <= 1024; (64 D + 1088) * 4 bytes of LDS (D <= 623), anything else is SAT_ERR_INVALID before a launch.
+ * Additive to ABI 8 (the 256-code tag bn_tdnnf_100h_vq_256). */
+int sat_vq_argmin_gather_tiled_f32(const float* z, const float* codebook, float* q, int32_t* idx,
+                                   float* dist, int B, int D, int T, int n_codes, void* stream);
+int sat_vq_argmin_gather_tiled_tie_f32(const float* z, const float* codebook, float* q, int32_t* idx, float* dist,
+                                       const float* pair_dist, float tie_scale, int32_t* tie_count,
+                                       int B, int D, int T, int n_codes, void* stream);
 
 /* pad frames at both ends: x [B][C][T] -> y [B][C][left+T+right].  Left = first frame replicated.
  * Right: interleave_right = 0 -> last frame replicated (F.pad(...,"replicate"),

@@ -123,6 +123,10 @@ _PROTOS = {
                                            C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sat_vq_argmin_gather_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sat_vq_argmin_gather_tiled_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sat_vq_argmin_gather_tiled_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sat_pad_replicate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p]),
     "sat_f0_stats_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -262,7 +262,24 @@ def build(args):
                 # ---- bottleneck extractor: compare the projections the VQ decides on, and the decisions
                 cfg = {k: getattr(ext, k) for k in ("precision", "w2v2_precision") if hasattr(ext, k)}
                 bn32 = None
-                if any(v != "f32" for v in cfg.values()):
+                has_vq = ext._has_vq() if hasattr(ext, "_has_vq") else True
+                if any(v != "f32" for v in cfg.values()) and not has_vq:
+                    # no quantiser (the *_aug tags): the bottleneck itself is what the generator reads; no indices, no flip report
+                    z = ext.extract_bn(wav.clone())
+                    keep_f32 = False
+                    try:
+                        for k in cfg:
+                            setattr(ext, k, "f32")
+                        bn32 = self.get_bn(wav)
+                        out["bn_extractor"] = relrms(z.permute(0, 2, 1), bn32)
+                        if not out["bn_extractor"] <= 5 * tol and fallback:
+                            fell.append("bn_extractor")
+                            keep_f32 = True
+                    finally:
+                        if not keep_f32:
+                            for k, v in cfg.items():
+                                setattr(ext, k, v)
+                elif any(v != "f32" for v in cfg.values()):
                     _, (z, idx, _) = ext.extract_bn(wav.clone(), want_aux=True)
                     keep_f32 = False
                     try:                                   # whatever happens in between (an OOM on the 16x slower exact kernels ...),

@@ -420,7 +420,10 @@ class _TdnnfBase(nn.Module):
                            x_split=xs if planes_in else None)
         aux = None
         if c.codebook is not None:
-            zq, idx, dist = ops.vq(z, c.codebook, want_dist=want_aux, tie=None if tie is None else (tie.pair, tie.scale, tie.counts))
+            # up to 64 codes the whole codebook sits in LDS (vq_kernel: the served 48 / 64-code tags keep their kernel and their bits);
+            # above, it is walked in tiles (vq_tiled_kernel: the 256-code tag)
+            vq = ops.vq if c.codebook.shape[0] <= 64 else ops.vq_tiled
+            zq, idx, dist = vq(z, c.codebook, want_dist=want_aux, tie=None if tie is None else (tie.pair, tie.scale, tie.counts))
             if tie is not None:
                 tie.idx = idx
             aux = (z, idx, dist)
@@ -440,9 +443,19 @@ class _TdnnfBase(nn.Module):
                        x_split=zs, y_split=ys, y_split_slope=1.0, **kw)
         return y, ys
 
+    def _has_vq(self):
+        """does the bottleneck layer hold a quantiser?  (tdnnf_vq.py / tdnnf_wav2vec2_vq.py: yes; tdnnf.py / tdnnf_wav2vec2.py, the
+        *_aug tags: no — the bottleneck is linearB's output as it is, and there is no decision to guard)"""
+        return hasattr(self._stack_layers()[-1], "bottleneck_func")
+
+    def _need_vq(self, what):
+        if not self._has_vq():
+            raise _lib.SatError(f"{what}: this extractor ({type(self).__name__}) has no VQ bottleneck, hence no indices")
+
     def vq_indices(self, wav):
         """VQ indices [N, T'] of `wav` [N, n] (device tensor; left untouched) as the extractor DELIVERS them: the configured
         arithmetic with the near-tie guard, flagged utterances decided again on the exact kernels.  -> (idx, rows decided again)"""
+        self._need_vq("vq_indices")
         with self._lock():
             feats = self._features_of(wav.clone())
             (zq, (_, idx, _)), status = self._run_stack_guarded(feats, want_aux=True)
@@ -452,6 +465,7 @@ class _TdnnfBase(nn.Module):
     def vq_flip_report(self, wav):
         """`vq_flip_stats` of this extractor as configured against its exact-f32 kernels on `wav` [N, n] (device tensor; left
         untouched): how many VQ indices the split-f16 arithmetic decides differently, and whether every one of them is a near-tie."""
+        self._need_vq("vq_flip_report")
         keys = [k for k in ("precision", "w2v2_precision") if hasattr(self, k)]
         cfg = {k: getattr(self, k) for k in keys}
         _, (z, idx, _) = self.extract_bn(wav.clone(), want_aux=True)
@@ -512,7 +526,7 @@ class _TdnnfBase(nn.Module):
         """-> (pair distances of the codebook [n, n], tie_scale) for sat_vq_argmin_gather_tie_f32, or None when the guard is off.
         tie_scale = 2 K sigma_rel / sqrt(D) with K = vq_tie_sigmas (`_tie_calibration`) — the error of d[a] - d[a'] is 2 dz . (e_a' - e_a),
         i.e. ~ N(0, (2 sigma_c |e_a - e_a'|)^2) with sigma_c = sigma_rel |z_t| / sqrt(D) per component."""
-        if not self.vq_tie_sigmas or self.__dict__.get("_tie_busy"):
+        if not self.vq_tie_sigmas or self.__dict__.get("_tie_busy") or not self._has_vq():
             return None
         if all(getattr(self, k) == "f32" for k in self._precision_keys()):
             return None
@@ -529,6 +543,8 @@ class _TdnnfBase(nn.Module):
         file stores (measured on the full model at export time, frozen.export_frozen)."""
         if self.__dict__.get("_frozen"):
             return self.__dict__.get("_tie_frozen")
+        if not self._has_vq():
+            return None
         if all(getattr(self, k) == "f32" for k in self._precision_keys()):
             return None
         key = tuple(getattr(self, k) for k in self._precision_keys()) + self._param_key() + (str(device),)
@@ -773,8 +789,9 @@ class TdnnfVqNet(_TdnnfBase):
         once the rest of its launches are enqueued, and repeats what it derived from those rows of bn)"""
         out, status = self._run_stack_guarded(feats)
         bn = out.permute(0, 2, 1)
-        st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
-        st["utterances"] += bn.shape[0] if status is not None else 0
+        if self._has_vq():
+            st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
+            st["utterances"] += bn.shape[0] if status is not None else 0
         if defer_ties:
             return bn, (TieFix(self, status, bn, feats, wav) if status is not None else None)
         self.resolve_ties(status, bn, feats, wav)
@@ -789,7 +806,7 @@ class TdnnfVqNet(_TdnnfBase):
             raise _lib.SatError("extract_bn expects a 2-dimensional tensor [N, samples]")
         x *= 32768
         feats = self.features(x.to(torch.float32))
-        if want_aux:                       # diagnostics: the arithmetic as configured, no second decision
+        if want_aux:                       # diagnostics: the arithmetic as configured, no second decision (aux None without a quantiser)
             out = self._run_stack(feats, want_aux=True)
             return out[0].permute(0, 2, 1), out[1]
         with self._lock():
@@ -805,3 +822,14 @@ class TdnnfVqNet(_TdnnfBase):
             raise _lib.SatError("forward expects a 2-dimensional tensor [N, samples]")
         x *= 32768
         return self._asr_outputs(self.features(x.to(torch.float32)))
+
+
+class TdnnfNet(TdnnfVqNet):
+    """fbank front end + 12 TDNNF layers, no quantiser (tdnnf.py:20-135; the *_aug tags): the state dict has no `bottleneck_func.*`
+    entries, `extract_bn` returns the 256-dim output of tdnnfs[-2]'s linearB (tdnnf.py:157-177) and there is no near-tie guard."""
+
+    def __init__(self, output_dim, hidden_dim=1024, bottleneck_dim=128, prefinal_bottleneck_dim=256,
+                 kernel_size_list=([3, 3, 3, 1, 3, 3, 3, 3, 3, 3, 3, 3], [1, 3, 3, 3]),
+                 subsampling_factor_list=([1, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1], [1.5, 1, 1, 1]), p_dropout=0.1):
+        super().__init__(output_dim, hidden_dim, bottleneck_dim, prefinal_bottleneck_dim, kernel_size_list, subsampling_factor_list,
+                         p_dropout, codebook_size=None)

@@ -110,7 +110,9 @@ def export_frozen(model, path, exact_extractor=False):
         raise _lib.SatError("export_frozen: the model is already a frozen one")
     ext = model.bn_extractor
     # (the calibration runs the extractor in both arithmetics: before the configured packings are taken)
-    cal = ext._tie_calibration(dev)
+    # (an extractor without a quantiser — the *_aug tags — has no decision to guard: no tie table, no exact-f32 packings in the file)
+    has_vq = ext._has_vq() if hasattr(ext, "_has_vq") else True
+    cal = ext._tie_calibration(dev) if has_vq else None
     gen._prepare(dev)
     ext._prepare(dev)
     blob = {"format": FORMAT, "kind": "anonymizer",
@@ -133,7 +135,7 @@ def export_frozen(model, path, exact_extractor=False):
         blob["extractor"]["mm_mode"] = int(ext._mm_mode)
         blob["extractor"]["w2v2_precision"] = ext.w2v2_precision
     # the exact-f32 packings of what is not configured as exact f32 (the wav2vec2 encoder's on request only)
-    need = [k for k in ext._precision_keys() if getattr(ext, k) != "f32"]
+    need = [k for k in ext._precision_keys() if getattr(ext, k) != "f32"] if has_vq else []
     if need and (exact_extractor or "w2v2_precision" not in need):
         exact = {}
         with ext._exact(ext):

@@ -19,6 +19,8 @@ _CONFIGS = {
     "local/tuning/hifigan.py": "anonymizer",
     "local/chain/tuning/tdnnf_vq.py": "tdnnf_vq",
     "local/chain/tuning/tdnnf_wav2vec2_vq.py": "tdnnf_wav2vec2_vq",
+    "local/chain/tuning/tdnnf.py": "tdnnf",                            # the same stacks without the quantiser (the *_aug tags)
+    "local/chain/tuning/tdnnf_wav2vec2.py": "tdnnf_wav2vec2",
     "local/tuning/ecapa_tdnn.py": "xvector",          # egs/asv/voxceleb: the ASV x-vector extractor
 }
 
@@ -38,6 +40,11 @@ def _builder(base_model_path):
     from . import asrbn
 
     def build(args):
+        if kind == "tdnnf":
+            return lambda **kw: asrbn.TdnnfNet(**kw)
+        if kind == "tdnnf_wav2vec2":
+            from . import wav2vec2
+            return lambda **kw: wav2vec2.TdnnfWav2vec2Net(**kw)
         cb = int(args.codebook_size) if args.codebook_size is not None else 48
         if kind == "tdnnf_vq":
             return lambda **kw: asrbn.TdnnfVqNet(codebook_size=cb, **kw)
@@ -52,9 +59,15 @@ def asrbn_conf_from_name(path):
     (`asrbn_model = ../../asr/librispeech/exp/chain/<name>/final.pt`, hifigan.py:27-29)"""
     name = os.path.basename(os.path.dirname(path))
     m = re.search(r"vq_(\d+)", name)
-    if m is None:
-        raise NotImplementedError(f"ASR-BN model '{name}' has no VQ bottleneck; only the *_vq_* tags are accelerated")
     w2v2 = "wav2vec2" in name
+    if m is None:
+        # no quantiser: tdnnf.py / tdnnf_wav2vec2.py, whose build(args) reads neither codebook_size nor freeze_encoder
+        return {
+            "task_path": "/egs/asr/librispeech",
+            "base_model_path": "local/chain/tuning/tdnnf_wav2vec2.py" if w2v2 else "local/chain/tuning/tdnnf.py",
+            "base_model_params": {"output_dim": 3280},
+            "base_model_args": {},
+        }
     return {
         "task_path": "/egs/asr/librispeech",
         "base_model_path": "local/chain/tuning/tdnnf_wav2vec2_vq.py" if w2v2 else "local/chain/tuning/tdnnf_vq.py",

@@ -120,8 +120,19 @@ def apply_conditioning(sd, cond):
     return sd
 
 
+# names whose conditioning IS another name's: the weights are drawn per key and seed, so nets with the same keys share them — the
+# `100h` and `600h` names, and a net without the quantiser and its VQ twin (the BatchNorm statistics of the layers below the
+# bottleneck do not see the codebook; a file's codebook entry has no key to land on in a net without one)
+_CONDITIONING_ALIAS = {
+    "bn_tdnnf_600h_aug": "bn_tdnnf_600h_vq_48",
+    "bn_tdnnf_100h_aug": "bn_tdnnf_600h_vq_48",
+    "bn_tdnnf_wav2vec2_100h_aug": "bn_tdnnf_wav2vec2_vq_48",
+}
+
+
 def conditioning_path(asr_name):
     here = os.path.dirname(os.path.abspath(__file__))
+    asr_name = _CONDITIONING_ALIAS.get(asr_name, asr_name)
     return os.path.join(here, "..", "tests", "golden", f"conditioning_{asr_name}.npz")
 
 

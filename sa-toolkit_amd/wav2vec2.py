@@ -379,8 +379,9 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         """stack + VQ with the near-tie guard (asrbn.TdnnfVqNet._bn_guarded)"""
         out, status = self._run_stack_guarded(feats)
         bn = out.permute(0, 2, 1)
-        st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
-        st["utterances"] += bn.shape[0] if status is not None else 0
+        if self._has_vq():
+            st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
+            st["utterances"] += bn.shape[0] if status is not None else 0
         if defer_ties:
             from .asrbn import TieFix
             return bn, (TieFix(self, status, bn, feats, wav) if status is not None else None)
@@ -424,3 +425,14 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         layers with the VQ layer run through, pad_input(padding_after), tdnnfs_after (1.5x subsampling first),
         the two prefinal layers and the output affines — the boundary to the Kaldi decoder"""
         return self._asr_outputs(self.features(x))
+
+
+class TdnnfWav2vec2Net(TdnnfWav2vec2VqNet):
+    """wav2vec2-large front end + TDNNF tail, no quantiser (tdnnf_wav2vec2.py:21-285; the wav2vec2 *_aug tag): no
+    `bottleneck_func.*` entries in the state dict, `extract_bn` returns linearB's 256-dim output (tdnnf_wav2vec2.py:221-243),
+    no near-tie guard."""
+
+    def __init__(self, output_dim, hidden_dim=1024, bottleneck_dim=128, prefinal_bottleneck_dim=256,
+                 kernel_size_list=([3, 3, 3], [1, 3, 3, 3]), subsampling_factor_list=([1, 1, 1], [1.5, 1, 1, 1]), p_dropout=0.1):
+        super().__init__(output_dim, hidden_dim, bottleneck_dim, prefinal_bottleneck_dim, kernel_size_list, subsampling_factor_list,
+                         p_dropout, codebook_size=None)
