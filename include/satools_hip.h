@@ -425,7 +425,8 @@ int sat_vq_argmin_gather_tiled_tie_f32(const float* z, const float* codebook, fl
  * tdnnf_wav2vec2_vq.py:299); interleave_right = 1 -> the reference's pad_input
  * (tdnnf_vq.py:228-234), whose right side tiles the last frames of ALL utterances of the batch
  * as one sequence: frame p of utterance b is the last frame of utterance (b*right + p) mod B.
- * sat_fbank_cmvn_pad_f32 applies the same pad_input rule. */
+ * sat_fbank_cmvn_pad_f32 applies the same pad_input rule.  Any number of rows B*C (the blocks of a
+ * grid column walk them). */
 int sat_pad_replicate_f32(const float* x, float* y, int B, int C, int T, int left, int right,
                           int interleave_right, void* stream);
 
@@ -434,6 +435,7 @@ int sat_pad_replicate_f32(const float* x, float* y, int B, int C, int T, int lef
  *     (chain/nn.py:267-304: `unfold` of the flattened [T*D] input with step int(1.5*D), so every other window
  *     straddles two frames; add_padd).  x [B][D][T] -> win, byp [B][D][Tq], Tq = (2(T-1))/3 + 1; the layer is a
  *     1x1 sat_conv1d_f32 on `win` with `byp` as residual (res_scale = bypass_scale).
+ *     B and D are grid dimensions: at most 65535 each (SAT_ERR_INVALID with a message beyond).
  *   sat_log_softmax_channels_f32: in place over C of x [B][C][T] (F.log_softmax(xent_out, dim=2)). */
 int sat_tdnnf_unfold15_f32(const float* x, float* win, float* byp, int B, int D, int T, void* stream);
 int sat_log_softmax_channels_f32(float* x, int B, int C, int T, void* stream);
@@ -450,7 +452,9 @@ int sat_log_softmax_channels_f32(float* x, int B, int C, int T, void* stream);
  *                      that are 0 after quantisation.
  *   sat_assemble_input_f32: x[b] = [ bn[b] (C_bn x T) ; nearest-interp f0[b] (1 x T_f0 -> T) ;
  *                      spk[b] (n_spk values, the one-hot row as f32) broadcast over T ]
- *                      (F.interpolate nearest + torch.cat, hifigan.py:91-97)
+ *                      (F.interpolate nearest + torch.cat, hifigan.py:91-97); B and the channel
+ *                      count C_bn + 1 + n_spk are grid dimensions: at most 65535 each
+ *                      (SAT_ERR_INVALID with a message beyond)
  * ------------------------------------------------------------------------------------------ */
 int sat_f0_stats_f32(const float* f0, int n, float* stats, void* stream);
 int sat_f0_apply_f32(float* f0, int n, const float* stats, int quant_bins, const float* noise,

@@ -429,6 +429,9 @@ extern "C" int sat_assemble_input_f32(const float* bn, const float* f0, const fl
                                       int C_bn, int T, int T_f0, int n_spk, void* stream) {
   SAT_REQUIRE(bn && f0 && (spk || n_spk == 0) && x, "assemble_input: null pointer");
   SAT_REQUIRE(B > 0 && C_bn > 0 && T > 0 && T_f0 > 0 && n_spk >= 0, "assemble_input: bad sizes");
+  // B and the channel count are grid dimensions y / z (at most 65535 blocks each)
+  SAT_REQUIRE(B < 65536, "assemble_input: batch of %d utterances exceeds the 65535 one launch takes", B);
+  SAT_REQUIRE((long long)C_bn + 1 + n_spk < 65536, "assemble_input: %lld channels exceed the 65535 one launch takes", (long long)C_bn + 1 + n_spk);
   dim3 grid(ceil_div(T, 256), C_bn + 1 + n_spk, B);
   hipLaunchKernelGGL(assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, bn, f0, spk, x, C_bn, T, T_f0, n_spk);
   SAT_LAUNCH_CHECK("assemble_kernel");
@@ -436,7 +439,10 @@ extern "C" int sat_assemble_input_f32(const float* bn, const float* f0, const fl
 }
 
 extern "C" int sat_tdnnf_unfold15_f32(const float* x, float* win, float* byp, int B, int D, int T, void* stream) {
-  SAT_REQUIRE(x && win && byp && B > 0 && D > 0 && D % 2 == 0 && T > 0 && B < 65536 && D < 65536, "tdnnf_unfold15: bad arguments");
+  SAT_REQUIRE(x && win && byp && B > 0 && D > 0 && D % 2 == 0 && T > 0, "tdnnf_unfold15: bad arguments");
+  // B and D are grid dimensions z / y (at most 65535 blocks each)
+  SAT_REQUIRE(B < 65536, "tdnnf_unfold15: batch of %d utterances exceeds the 65535 one launch takes", B);
+  SAT_REQUIRE(D < 65536, "tdnnf_unfold15: %d channels exceed the 65535 one launch takes", D);
   const int Tq = (2 * (T - 1)) / 3 + 1;
   hipLaunchKernelGGL(tdnnf_unfold15_kernel, dim3(ceil_div(Tq, 256), D, B), dim3(256), 0, (hipStream_t)stream, x, win, byp, D, T, Tq);
   SAT_LAUNCH_CHECK("tdnnf_unfold15_kernel");

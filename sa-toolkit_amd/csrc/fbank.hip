@@ -186,23 +186,27 @@ __global__ void __launch_bounds__(256) cmvn_pad_kernel(const float* __restrict__
   }
 }
 
+// the grid has at most 65535 rows of blocks (the documented y limit; 64 utterances of 1024 channels are one row past it): a block walks
+// every gridDim.y-th row of its column
 __global__ void __launch_bounds__(256) pad_replicate_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                             int T, int left, int right, int C, int B,
                                                             int interleave) {
-  const int row = blockIdx.y;
-  const int b = row / C, c = row - b * C;
   const int To = left + T + right;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= To) return;
-  float v;
-  if (t < left + T) {
-    const int s = t < left ? 0 : t - left;
-    v = x[(size_t)row * T + s];
-  } else {
-    const int srow = right_pad_source(b, t - left - T, right, B, interleave) * C + c;
-    v = x[(size_t)srow * T + (T - 1)];
+  const long long rows = (long long)B * C;
+  for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = (int)(row / C), c = (int)(row - (long long)b * C);
+    float v;
+    if (t < left + T) {
+      const int s = t < left ? 0 : t - left;
+      v = x[(size_t)row * T + s];
+    } else {
+      const size_t srow = (size_t)right_pad_source(b, t - left - T, right, B, interleave) * C + c;
+      v = x[srow * T + (T - 1)];
+    }
+    y[(size_t)row * To + t] = v;
   }
-  y[(size_t)row * To + t] = v;
 }
 
 }  // namespace sat
@@ -244,7 +248,9 @@ extern "C" int sat_fbank_cmvn_pad_f32(const float* wav, float* feats, const floa
 extern "C" int sat_pad_replicate_f32(const float* x, float* y, int B, int C, int T, int left, int right,
                                      int interleave_right, void* stream) {
   SAT_REQUIRE(x && y && B > 0 && C > 0 && T > 0 && left >= 0 && right >= 0, "pad_replicate: bad arguments");
-  dim3 grid(ceil_div(left + T + right, 256), B * C);
+  SAT_REQUIRE((long long)left + T + right <= INT32_MAX, "pad_replicate: padded length %lld exceeds int32", (long long)left + T + right);
+  const long long rows = (long long)B * C;
+  dim3 grid(ceil_div(left + T + right, 256), (unsigned)(rows < 65535 ? rows : 65535));
   hipLaunchKernelGGL(pad_replicate_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, T, left, right, C, B, interleave_right);
   SAT_LAUNCH_CHECK("pad_replicate_kernel");
   return SAT_OK;
