@@ -599,6 +599,39 @@ int sat_res2_chain_f32(const float* y, float* z, const float* w, const float* sc
 int sat_linear_rows_f32(const float* x, const float* w, const float* bias, const float* ch_scale, const float* ch_shift, int relu,
                         float* y, int B, int Cin, int Cout, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ASV evaluation: what the x-vectors are extracted for (satools/sidekit/objf.py:268-369 compute_metrics and
+ * satools/sidekit/scoring/__init__.py:7-55 asnorm / cosine_scoring).  Added under ABI 8: a library built before these entries
+ * existed lacks the symbols, which the Python binding reports with the build command.  csrc/asv_score.hip.
+ *   sat_cohort_topk_stats_f32    scoring/__init__.py:25-39 (the einsum, topk, mean and std of asnorm), once per VECTOR instead of once
+ *                                per trial: for every row of x [N][D] the C plain dot products with cohort [C][D], the k largest of
+ *                                them, their mean [N] and unbiased standard deviation [N] (torch.std; k = 1 gives NaN).  The scores
+ *                                live in LDS only: no workspace, nothing of size N x C in memory.  1 <= k <= C <= 8192, D <= 512,
+ *                                D % 4 == 0, x and cohort 16-byte aligned, any N; anything else is SAT_ERR_INVALID before a launch.
+ *                                Ties at the k-th place do not change the result (the threshold value is counted k - count_above times);
+ *                                the deviation is summed around the mean in a second pass.
+ *   sat_trial_scores_f32         scoring/__init__.py:47-55 (1 - scipy cosine distance per trial) and :42-44 (the s-norm of asnorm):
+ *                                score[m] = a.b / (|a| |b|), a = enroll[idx_e[m]] of [E][D], b = test[idx_t[m]] of [T][D]; with the four
+ *                                statistics (all or none; mu_e / sd_e [E], mu_t / sd_t [T]) also
+ *                                score_asnorm[m] = ((s - mu_e[ie]) / sd_e[ie] + (s - mu_t[it]) / sd_t[it]) / 2.  idx_e / idx_t are HOST
+ *                                arrays of M entries: an index outside its table is SAT_ERR_INVALID before anything is launched; they
+ *                                are copied into idx_dev (device, 2 M entries) on the stream.
+ *   sat_segment_mean_l2norm_f32  objf.py:272-281, the enrolment vector of a speaker: out[s] = mean of the rows x[order[u]],
+ *                                offsets[s] <= u < offsets[s + 1], divided by its L2 norm; a speaker with ONE utterance gets that row
+ *                                bit for bit (the extractor has normalised it already).  x [U][D], out [S][D]; order [U] and
+ *                                offsets [S + 1] are HOST arrays, checked here and copied into seg_dev (device, U + S + 1 entries).
+ * The host index arrays of the last two entries may be ordinary (pageable) memory and may be freed or changed as soon as the call
+ * returns: the runtime stages a pageable host-to-device copy before hipMemcpyAsync returns, and the entries rely on that.  For the same
+ * reason (a host-side check and a staged copy per call) these two entries cannot be recorded into a stream capture / hipGraph;
+ * sat_cohort_topk_stats_f32 can.
+ * ------------------------------------------------------------------------------------------ */
+int sat_cohort_topk_stats_f32(const float* x, const float* cohort, int N, int C, int D, int k, float* mean, float* std, void* stream);
+int sat_trial_scores_f32(const float* enroll, const float* test, const int32_t* idx_e, const int32_t* idx_t, int32_t* idx_dev, int E, int T,
+                         int M, int D, const float* mu_e, const float* sd_e, const float* mu_t, const float* sd_t, float* score,
+                         float* score_asnorm, void* stream);
+int sat_segment_mean_l2norm_f32(const float* x, const int32_t* order, const int32_t* offsets, int32_t* seg_dev, int U, int S, int D,
+                                float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,12 @@ _PROTOS = {
     "sat_pcm16_from_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "sat_assemble_input_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_void_p]),
+    # ASV evaluation (csrc/asv_score.hip): added under ABI 8, see lib()
+    "sat_cohort_topk_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sat_trial_scores_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sat_segment_mean_l2norm_f32": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -195,7 +201,12 @@ def lib():
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in _PROTOS.items():
-            fn = getattr(l, name)
+            try:
+                fn = getattr(l, name)
+            except AttributeError:
+                # entries are added without a new ABI number: a library built from an older tree passes the version check below
+                raise SatError(f"{LIB_PATH} does not export {name}: it was built from an older source tree; rebuild it with "
+                               "`python sa-toolkit_amd/build.py`") from None
             fn.restype = res
             fn.argtypes = args
         if l.sat_abi_version() != 8:       # 5: SAT_CONV_F16F8R; sat_conv1d_desc grew x_split8 / y_split8 / y_split_hi_only.  6: sat_pcm16_*.  7: VQ near-tie count, hifigan get_option / range probe.  8: sat_tdnnf_layer_f32

@@ -1,0 +1,315 @@
+"""ASV privacy evaluation: how well does the anonymisation hide the speaker?
+(reference: egs/anon/vctk/local/eval.py:196-231 -> satools/sidekit/model.py:208-239 `--mode eval` ->
+satools/sidekit/objf.py:186-369 `test` / `compute_metrics` -> satools/sidekit/scoring/__init__.py:7-55 and scoring/metric.py)
+
+`test_metrics` extracts the enrolment and trial x-vectors with the ECAPA-TDNN extractor of this package, `compute_metrics`
+averages the enrolment vectors per speaker, cosine-scores the trial list, applies adaptive s-norm against a cohort and computes
+linkability, min Cllr and the EER.  The arithmetic over vectors runs on the device (csrc/asv_score.hip):
+
+  per-speaker enrolment vectors            ops.segment_mean_l2norm
+  cohort statistics of adaptive s-norm     ops.cohort_topk_stats — once per unique speaker and per unique test utterance, not once
+                                           per trial as the reference computes them; the score matrices never exist
+  cosine score and s-norm of every trial   ops.trial_scores
+
+The metrics are functions of the M scores alone and run on the host in float64 numpy: `linkability` (Gomez-Barrero et al. 2017, as
+adapted by the reference's metric.py:10-68), `min_cllr` with the PAV calibration (Bruemmer & du Preez 2006; metric.py:250-535) and
+the ROCCH-EER of that calibration.  They are written from the papers' formulae and the reference's conventions (bin rule, tie
+order, the monotonicity ramp), with a linear-time stack PAV in place of the reference's Python loop.
+
+EER: the reference takes `eer`, its bootstrap interval and the threshold from the third-party `feerci` package.  When `feerci` can be
+imported it is called exactly as objf.py:332 calls it; otherwise `eer` is the ROCCH-EER x 100, `eer_threshold` the calibrated LLR of
+the ROCCH segment that crosses the diagonal, and `eer_lower` / `eer_upper` are None (parity unpinned: INTEGRATION.md)."""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+TOP_K = 200          # scoring/__init__.py:26
+
+
+# ---- metrics on the host (float64) ---------------------------------------------------------------------------------
+def linkability(mated, non_mated, omega=1.0, n_bins=-1):
+    """global linkability D_sys of two score sets -> (D_sys, D per bin, bin centres, bin edges).
+    Bins: min(len(mated) // 10, 100) equal bins from the smallest to the largest score of both sets; local measure
+    D = 2 w LR / (1 + w LR) - 1 where w LR > 1, else 0, with LR the ratio of the two normalised histograms (LR = 1 where the
+    non-mated histogram is empty and the mated one too, D = 1 where only the non-mated one is); D_sys = trapezoid rule of D x the
+    mated density over the bin centres."""
+    mated = np.asarray(mated, dtype=np.float64)
+    non_mated = np.asarray(non_mated, dtype=np.float64)
+    if n_bins < 0:
+        n_bins = min(int(len(mated) / 10), 100)
+    if n_bins < 1:             # fewer than 10 mated scores: no bin, nothing to integrate (the reference's histogram call fails here)
+        return 0.0, np.zeros(0), np.zeros(0), np.zeros(0)
+    lo = min(mated.min(), non_mated.min())
+    hi = max(mated.max(), non_mated.max())
+    edges = np.linspace(lo, hi, num=n_bins + 1, endpoint=True)
+    centres = (edges[1:] + edges[:-1]) / 2
+    dens_m = np.histogram(mated, bins=edges, density=True)[0]
+    dens_n = np.histogram(non_mated, bins=edges, density=True)[0]
+    lr = np.ones_like(dens_m)
+    has_n = dens_n != 0
+    lr[has_n] = dens_m[has_n] / dens_n[has_n]
+    wlr = omega * lr
+    local = 2 * (wlr / (1 + wlr)) - 1
+    local[wlr <= 1] = 0
+    local[(~has_n) & (dens_m != 0)] = 1
+    f = local * dens_m
+    d_sys = float(np.sum((centres[1:] - centres[:-1]) * (f[1:] + f[:-1]) / 2.0)) if len(centres) > 1 else 0.0
+    return d_sys, local, centres, edges
+
+
+def pav(y):
+    """pool adjacent violators: the non-decreasing fit of y that is closest in squares -> (fit [n], block widths, block heights).
+    One pass with a stack of (sum, count) blocks: a new point is a block; while the block below is not lower it is merged in."""
+    y = np.asarray(y, dtype=np.float64)
+    n = y.shape[0]
+    if y.ndim != 1 or n == 0:
+        raise ValueError("pav: a non-empty vector is needed")
+    sums = np.empty(n)
+    counts = np.empty(n, dtype=np.int64)
+    top = -1
+    for v in y.tolist():
+        top += 1
+        sums[top], counts[top] = v, 1
+        # (means compared as s_a n_b >= s_b n_a: exact for the 0 / 1 labels of the calibration)
+        while top > 0 and sums[top - 1] * counts[top] >= sums[top] * counts[top - 1]:
+            sums[top - 1] += sums[top]
+            counts[top - 1] += counts[top]
+            top -= 1
+    widths = counts[:top + 1].copy()
+    heights = sums[:top + 1] / widths
+    return np.repeat(heights, widths), widths, heights
+
+
+def _logit(p):
+    out = np.empty_like(p)
+    mid = (p > 0) & (p < 1)
+    out[mid] = np.log(p[mid] / (1 - p[mid]))
+    out[p <= 0] = -np.inf
+    out[p >= 1] = np.inf
+    return out
+
+
+def cllr(tar_llrs, non_llrs):
+    """application-independent cost of log-likelihood ratios, in bits (Bruemmer & du Preez 2006)"""
+    with np.errstate(over="ignore", divide="ignore"):
+        p_tar = 1 / (1 + np.exp(-np.asarray(tar_llrs, dtype=np.float64)))
+        p_non = 1 / (1 + np.exp(np.asarray(non_llrs, dtype=np.float64)))
+        if np.any(p_tar == 0) or np.any(p_non == 0):
+            return float("inf")
+        ln2 = np.log(2)
+        return float(((-np.log(p_tar)).mean() / ln2 + (-np.log(p_non)).mean() / ln2) / 2)
+
+
+def calibrate(tar, non, monotonicity_epsilon=1e-6):
+    """optimal (PAV) calibration of two score sets -> dict: tar_llrs / non_llrs (in the input order), eer = the ROCCH-EER as a
+    fraction, eer_threshold = the calibrated LLR of the ROCCH segment that crosses the diagonal.
+    Scores are sorted stably with the non-targets first among ties; the ideal posteriors (0 / 1 labels) are fitted by `pav`,
+    turned into log-odds, the prior log-odds len(tar) / len(non) taken off, and a ramp of epsilon i / N added to keep them
+    strictly ordered.  The ROC convex hull has one vertex per PAV block boundary; its EER is the largest diagonal crossing
+    det / (dy + dx) over the hull's segments, axis-parallel segments counting as 0."""
+    tar = np.asarray(tar, dtype=np.float64)
+    non = np.asarray(non, dtype=np.float64)
+    n_tar, n_non = len(tar), len(non)
+    n = n_tar + n_non
+    scores = np.concatenate([non, tar])
+    labels = np.concatenate([np.zeros(n_non), np.ones(n_tar)])
+    order = np.argsort(scores, kind="mergesort")
+    labels = labels[order]
+    fit, widths, heights = pav(labels)
+    with np.errstate(divide="ignore"):
+        prior = np.log(n_tar / n_non)
+        llrs = _logit(fit) - prior
+        block_llrs = _logit(heights) - prior
+    llrs = llrs + np.arange(n) * monotonicity_epsilon / n
+    back = np.empty(n, dtype=np.int64)
+    back[order] = np.arange(n)
+    llrs = llrs[back]
+    # ROCCH vertices: threshold to the left of block i -> i scores-blocks rejected
+    left = np.concatenate([[0], np.cumsum(widths)])
+    tar_below = np.concatenate([[0.0], np.cumsum(labels)])[left]              # targets rejected: misses
+    non_above = (n - left) - (n_tar - tar_below)                              # non-targets accepted: false alarms
+    pmiss = tar_below / n_tar
+    pfa = non_above / n_non
+    x0, x1, y0, y1 = pfa[:-1], pfa[1:], pmiss[:-1], pmiss[1:]
+    if not (np.all(x1 <= x0) and np.all(y0 <= y1)):
+        raise AssertionError("ROCCH vertices are not ordered")
+    dx, dy = x0 - x1, y1 - y0
+    live = (dx != 0) & (dy != 0)
+    cross = np.zeros(len(dx))
+    cross[live] = (x0[live] * y1[live] - x1[live] * y0[live]) / (dy[live] + dx[live])
+    eer = float(cross.max()) if len(cross) else 0.0
+    thr = float(block_llrs[int(np.argmax(cross))]) if eer > 0 else 0.0
+    return {"tar_llrs": llrs[n_non:], "non_llrs": llrs[:n_non], "eer": max(eer, 0.0), "eer_threshold": thr}
+
+
+def min_cllr(tar, non, monotonicity_epsilon=1e-6):
+    """Cllr of the optimally calibrated scores -> (min Cllr, ROCCH-EER, calibrated target LLRs, calibrated non-target LLRs)"""
+    c = calibrate(tar, non, monotonicity_epsilon)
+    return cllr(c["tar_llrs"], c["non_llrs"]), c["eer"], c["tar_llrs"], c["non_llrs"]
+
+
+def score_metrics(mated, non_mated):
+    """the reference's metric set of one pair of score sets (objf.py:330-339) -> (dict, calibrated mated, calibrated non-mated)"""
+    d_sys = linkability(mated, non_mated)[0]
+    c = calibrate(mated, non_mated)
+    cmin = cllr(c["tar_llrs"], c["non_llrs"])
+    try:
+        from feerci import feerci
+    except ImportError:
+        eer, lower, upper, thr = c["eer"] * 100, None, None, c["eer_threshold"]
+    else:
+        eer, lower, upper, _boot, thr = feerci(c["non_llrs"], c["tar_llrs"], is_sorted=False, return_threshold=True)
+        eer, lower, upper, thr = float(eer * 100), float(lower * 100), float(upper * 100), float(thr)
+    return ({"linkability": d_sys, "eer": eer, "eer_lower": lower, "eer_upper": upper, "min_cllr": cmin, "eer_threshold": thr},
+            c["tar_llrs"], c["non_llrs"])
+
+
+# ---- scoring on the device -----------------------------------------------------------------------------------------
+def read_trials(trials_file):
+    """`enrol-speaker test-utterance target|nontarget` per line -> (speakers, utterances, labels)"""
+    spk, utt, lab = [], [], []
+    with open(trials_file) as f:
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if len(t) < 3:
+                raise _lib.SatError(f"{trials_file}: a trial line needs `enrol test target|nontarget`, got '{line.strip()}'")
+            spk.append(t[0]), utt.append(t[1]), lab.append(t[2])
+    if not spk:
+        raise _lib.SatError(f"{trials_file}: no trials")
+    return spk, utt, lab
+
+
+def _stack(vectors, device):
+    """vectors of one length, all on one device -> [n, D] float32 on `device` (one stack, one copy)"""
+    rows = [torch.as_tensor(v).detach().reshape(-1) for v in vectors]
+    if len({r.device for r in rows}) > 1:
+        rows = [r.to(device) for r in rows]
+    return torch.stack(rows).to(device=device, dtype=torch.float32).contiguous()
+
+
+def score_trials(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, spk_of_trial, utt_of_trial, cohort=None, device=None):
+    """-> (score [M], score_asnorm [M] or None) as float32 numpy arrays, in trial order.  Every enrolment speaker and every
+    distinct test utterance is one row on the device; the trial list only carries their row numbers."""
+    if device is None:
+        first = next(iter(utt2embd_enroll.values()))
+        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device("cuda")
+    speakers = list(enroll_spk2utt)
+    order_utts, offsets = [], [0]
+    for s in speakers:
+        utts = enroll_spk2utt[s]
+        if not utts:
+            raise _lib.SatError(f"enrolment speaker {s} has no utterance")
+        order_utts += utts
+        offsets.append(len(order_utts))
+    missing = [u for u in order_utts if u not in utt2embd_enroll]
+    if missing:
+        raise _lib.SatError(f"no enrolment x-vector for {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+    enroll = ops.segment_mean_l2norm(_stack([utt2embd_enroll[u] for u in order_utts], device), np.arange(len(order_utts)), offsets)
+    spk_row = {s: i for i, s in enumerate(speakers)}
+    utt_row = {}
+    for u in utt_of_trial:
+        if u not in utt_row:
+            if u not in utt2embd_trial:
+                raise _lib.SatError(f"no trial x-vector for {u}")
+            utt_row[u] = len(utt_row)
+    unknown = [s for s in spk_of_trial if s not in spk_row]
+    if unknown:
+        raise _lib.SatError(f"the trial list names speakers without enrolment: {unknown[:3]}")
+    test = _stack([utt2embd_trial[u] for u in utt_row], device)
+    idx_e = np.fromiter((spk_row[s] for s in spk_of_trial), dtype=np.int32, count=len(spk_of_trial))
+    idx_t = np.fromiter((utt_row[u] for u in utt_of_trial), dtype=np.int32, count=len(utt_of_trial))
+    if cohort is None:
+        return ops.trial_scores(enroll, test, idx_e, idx_t).cpu().numpy(), None
+    cohort = torch.as_tensor(cohort).detach().to(device=device, dtype=torch.float32).contiguous()
+    k = min(TOP_K, cohort.shape[0])
+    mu_e, sd_e = ops.cohort_topk_stats(enroll, cohort, k)
+    mu_t, sd_t = ops.cohort_topk_stats(test, cohort, k)
+    score, score_as = ops.trial_scores(enroll, test, idx_e, idx_t, (mu_e, sd_e, mu_t, sd_t))
+    return score.cpu().numpy(), score_as.cpu().numpy()
+
+
+def compute_metrics(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, trials_file, out_scores, cohort=None, device=None):
+    """objf.py:268-369: x-vectors by utterance, the enrolment speakers' utterance lists, the trial list -> the metric dict
+    (`linkability`, `eer`, `eer_lower`, `eer_upper`, `min_cllr`, `eer_threshold`, `asnorm` = the same six after adaptive s-norm
+    against `cohort` (None without one), `score` = the calibrated (mated, non-mated) LLRs of the last set computed).
+    Writes `<out_scores>/scores`: `enrol test score` per trial."""
+    spk, utt, lab = read_trials(trials_file)
+    score, score_as = score_trials(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, spk, utt, cohort=cohort, device=device)
+    os.makedirs(out_scores, exist_ok=True)
+    with open(os.path.join(out_scores, "scores"), "w") as f:
+        for s, u, v in zip(spk, utt, score.tolist()):
+            f.write(f"{s} {u} {v!r}\n")
+    lab = np.asarray(lab)
+    tar, non = lab == "target", lab == "nontarget"
+    if not tar.any() or not non.any():
+        raise _lib.SatError(f"{trials_file}: the metrics need target and nontarget trials")
+    metrics, mated, non_mated = score_metrics(score[tar].astype(np.float64), score[non].astype(np.float64))
+    metrics["asnorm"] = {k: None for k in ("eer", "linkability", "eer_lower", "eer_upper", "min_cllr", "eer_threshold")}
+    if score_as is not None:
+        m_as, mated, non_mated = score_metrics(score_as[tar].astype(np.float64), score_as[non].astype(np.float64))
+        metrics["asnorm"].update(m_as)
+    metrics["score"] = (mated, non_mated)
+    return metrics
+
+
+def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_file, out_dir, as_norm=True):
+    """objf.py:189-266: extract, score, measure.  Writes `<out_dir>/xvectors.npz` (`utts`, `xvectors`), `scores` and `metric.json`
+    and returns the metric dict.  One utterance per extractor call, as the reference (the kernels take no per-utterance lengths,
+    and zero padding would change the InstanceNorm and the pooling); an utterance of both lists is extracted once."""
+    from .pipeline import load_wav_from_scp, read_wav_scp
+    model.eval()
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise _lib.SatError("x-vector extraction runs on the HIP device only: move the model there first (no CPU fallback)")
+    enroll_scp, trials_scp = read_wav_scp(enroll_wav_scp), read_wav_scp(trials_wav_scp)
+    spk2utt = {}
+    for u, s in read_wav_scp(enroll_utt2spk).items():
+        spk2utt.setdefault(s, []).append(u)
+
+    def extract(entry):
+        wav, _sr = load_wav_from_scp(entry)
+        with torch.no_grad():
+            _, xv = model(wav.squeeze().to(device), target=None)
+        return xv.reshape(-1)
+
+    enroll = {u: extract(e) for u, e in enroll_scp.items()}
+    trial = {u: enroll[u] if u in enroll else extract(e) for u, e in trials_scp.items()}
+    cohort = None
+    if as_norm and hasattr(model, "after_speaker_embedding"):
+        cohort = torch.nn.functional.normalize(model.after_speaker_embedding.weight.data, dim=1)
+    os.makedirs(out_dir, exist_ok=True)
+    both = dict(enroll)
+    both.update(trial)
+    np.savez(os.path.join(out_dir, "xvectors.npz"), utts=np.asarray(list(both)),
+             xvectors=torch.stack(list(both.values())).cpu().numpy())
+    metrics = compute_metrics(enroll, trial, spk2utt, trials_file, out_dir, cohort=cohort, device=device)
+    with open(os.path.join(out_dir, "metric.json"), "w") as f:
+        json.dump({k: v for k, v in metrics.items() if k != "score"}, f, indent=1)
+    return metrics
+
+
+test_metrics.__test__ = False      # (a library function, not a pytest case)
+
+
+def main(argv=None):
+    import argparse
+    from .infer_helper import load_model
+    ap = argparse.ArgumentParser(prog="asv-eval", description="ASV privacy metrics of a data directory (EER, min Cllr, linkability)")
+    ap.add_argument("checkpoint", help="x-vector checkpoint (final.pt), or synthetic:xvector[?seed=N&speakers=K]")
+    ap.add_argument("--enrolls-wav-scp", required=True)
+    ap.add_argument("--trails-wav-scp", required=True)
+    ap.add_argument("--enroll-utt2spk", required=True)
+    ap.add_argument("--trials", required=True)
+    ap.add_argument("--decode-output", required=True, help="directory for xvectors.npz, scores and metric.json")
+    ap.add_argument("--no-as-norm", action="store_true", help="skip adaptive s-norm")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    model = load_model(a.checkpoint).to(a.device)
+    m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm)
+    print(json.dumps({k: v for k, v in m.items() if k != "score"}))

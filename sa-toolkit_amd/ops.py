@@ -645,3 +645,86 @@ def log_softmax_channels_(x):
     B, c, t = x_.shape
     check(lib().sat_log_softmax_channels_f32(ptr(x_), B, c, t, stream()), "sat_log_softmax_channels_f32")
     return x_
+
+
+# ---- ASV evaluation (csrc/asv_score.hip) ---------------------------------------------------------------
+def _host_i32(v, what):
+    """an index list (anything numpy takes, or a CPU tensor) -> (contiguous int32 numpy array, ctypes pointer)"""
+    import numpy as np
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            raise _lib.SatError(f"{what}: index lists are host arrays (they are checked before the launch)")
+        v = v.numpy()
+    a = np.asarray(v)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+        raise _lib.SatError(f"{what}: a non-empty one-dimensional integer list is needed, got {a.dtype} {a.shape}")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise _lib.SatError(f"{what}: values do not fit 32 bits")
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _rows2(t, what):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
+        raise _lib.SatError(f"{what}: a two-dimensional float32 device tensor is needed")
+    return t.contiguous()
+
+
+def cohort_topk_stats(x, cohort, k=None):
+    """x [N, D], cohort [C, D] -> (mean [N], std [N]) of the k largest of the C dot products of every row (asnorm's topk statistics,
+    scoring/__init__.py:25-39; k defaults to min(200, C)); the N x C scores stay in LDS"""
+    x, cohort = _rows2(x, "cohort_topk_stats: x"), _rows2(cohort, "cohort_topk_stats: cohort")
+    (N, D), (Cn, Dc) = x.shape, cohort.shape
+    if D != Dc or N == 0:
+        raise _lib.SatError(f"cohort_topk_stats: x {tuple(x.shape)} does not fit cohort {tuple(cohort.shape)}")
+    k = min(200, Cn) if k is None else int(k)
+    mean = torch.empty(N, dtype=torch.float32, device=x.device)
+    std = torch.empty(N, dtype=torch.float32, device=x.device)
+    check(lib().sat_cohort_topk_stats_f32(ptr(x), ptr(cohort), N, Cn, D, k, ptr(mean), ptr(std), stream()), "sat_cohort_topk_stats_f32")
+    return mean, std
+
+
+def trial_scores(enroll, test, idx_e, idx_t, stats=None):
+    """cosine score of every trial (enroll[idx_e[m]], test[idx_t[m]]) -> score [M]; with stats = (mu_e, sd_e, mu_t, sd_t), the cohort
+    statistics of the enrolment and of the test rows, also the adaptive s-norm score [M] -> (score, score_asnorm).
+    idx_e / idx_t are host index lists: checked by the entry before anything is launched and copied to the device by a staged
+    (pageable) copy, so they may be dropped on return — and the call cannot be recorded into a torch.cuda.graph"""
+    enroll, test = _rows2(enroll, "trial_scores: enroll"), _rows2(test, "trial_scores: test")
+    ie, pe = _host_i32(idx_e, "trial_scores: idx_e")
+    it, pt = _host_i32(idx_t, "trial_scores: idx_t")
+    (E, D), (T, Dt) = enroll.shape, test.shape
+    if D != Dt or E == 0 or T == 0 or ie.size != it.size:
+        raise _lib.SatError(f"trial_scores: enroll {tuple(enroll.shape)}, test {tuple(test.shape)}, {ie.size} and {it.size} indices do not fit")
+    M = ie.size
+    dev = enroll.device
+    st = [None] * 4
+    if stats is not None:
+        if len(stats) != 4:
+            raise _lib.SatError("trial_scores: stats = (mu_e, sd_e, mu_t, sd_t)")
+        for i, (s, n) in enumerate(zip(stats, (E, E, T, T))):
+            if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or tuple(s.shape) != (n,) or not s.is_cuda:
+                raise _lib.SatError(f"trial_scores: statistic {i} must be a float32 device vector of {n} values")
+            st[i] = s.contiguous()
+    score = torch.empty(M, dtype=torch.float32, device=dev)
+    score_as = torch.empty(M, dtype=torch.float32, device=dev) if stats is not None else None
+    idx_dev = torch.empty(2 * M, dtype=torch.int32, device=dev)
+    check(lib().sat_trial_scores_f32(ptr(enroll), ptr(test), pe, pt, ptr(idx_dev), E, T, M, D, ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]),
+                                     ptr(score), ptr(score_as), stream()), "sat_trial_scores_f32")
+    return score if stats is None else (score, score_as)
+
+
+def segment_mean_l2norm(x, order, offsets):
+    """x [U, D] -> [S, D]: row s = the mean of x[order[offsets[s]:offsets[s + 1]]] over its L2 norm, or that row itself, bit for bit, when
+    the segment holds one (objf.py:272-281).  order / offsets are host index lists (checked and copied like those of trial_scores:
+    not for use under torch.cuda.graph)"""
+    x = _rows2(x, "segment_mean_l2norm: x")
+    o, po = _host_i32(order, "segment_mean_l2norm: order")
+    f, pf = _host_i32(offsets, "segment_mean_l2norm: offsets")
+    U, D = x.shape
+    S = f.size - 1
+    if U == 0 or o.size != U or S < 1:
+        raise _lib.SatError(f"segment_mean_l2norm: x {tuple(x.shape)}, {o.size} order entries and {f.size} offsets do not fit")
+    out = torch.empty(S, D, dtype=torch.float32, device=x.device)
+    seg_dev = torch.empty(U + S + 1, dtype=torch.int32, device=x.device)
+    check(lib().sat_segment_mean_l2norm_f32(ptr(x), po, pf, ptr(seg_dev), U, S, D, ptr(out), stream()), "sat_segment_mean_l2norm_f32")
+    return out

@@ -176,16 +176,24 @@ def checkpoint(tag, seed=0, conditioning="auto"):
 
 
 def load(spec, option_args=None):
-    """`synthetic:<tag>[?seed=N]` -> model with seeded weights (see infer_helper.load_model)"""
+    """`synthetic:<tag>[?seed=N]` (or `synthetic:xvector[?seed=N&speakers=K]`) -> model with seeded weights (see infer_helper.load_model)"""
     from . import infer_helper
     from .anonymizer import SimpleNamespace
     body = spec[len("synthetic:"):]
     tag, _, query = body.partition("?")
-    seed = 0
+    seed, speakers = 0, 10
     for kv in filter(None, query.split("&")):
         k, _, v = kv.partition("=")
         if k == "seed":
             seed = int(v)
+        if k == "speakers":
+            speakers = int(v)
+    if tag == "xvector":
+        # the ASV x-vector extractor (ECAPA-TDNN), `speakers` = rows of its AAM-softmax layer: the cohort of adaptive s-norm
+        from . import xvector
+        net = xvector.build()(num_speakers=speakers)
+        net.load_state_dict(xvector_state(seed, speakers), strict=True)
+        return net
     state, net = checkpoint(tag, seed)
     if option_args:
         args = dict(state["base_model_args"])
