@@ -632,6 +632,39 @@ int sat_trial_scores_f32(const float* enroll, const float* test, const int32_t* 
 int sat_segment_mean_l2norm_f32(const float* x, const int32_t* order, const int32_t* offsets, int32_t* seg_dev, int U, int S, int D,
                                 float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ResNet x-vector extractor (half-ResNet34 with squeeze-excitation, attentive pooling with global context;
+ * egs/asv/voxceleb/local/tuning/resnet.py:17-79).  Added under ABI 8 like the ASV entries above.  csrc/conv2d.hip.
+ * AXES: images are [B][C][H][W], W contiguous.  The net keeps TIME on W and frequency on H — the reference runs [B, C, T, 80],
+ * frequency innermost (archi.py:110-113); a 3x3 conv commutes with transposing both the image and the kernel, so the packed weights
+ * carry the transpose and the last layer's [B][256][10][T'] IS the [B][2560][T'] tensor pooling.py:126-128 builds by a permute.
+ *   sat_conv2d_f32             torch.nn.Conv2d(bias=False) of archi.py:90-95 and nn.py:40-44, :52-53 with the BatchNorm2d in eval that
+ *                              follows it (archi.py:114, nn.py:63-64, :54) and nn.py:63's ReLU:
+ *                                y[b][co][ho][wo] = act(ch_scale[co] * sum_{ci,kh,kw} w[co][ci][kh][kw] x[b][ci][s ho - p + kh][s wo - p + kw]
+ *                                                       + ch_shift[co]),   x = 0 outside the image
+ *                              ksize 3 (p = 1) or 1 (p = 0); stride s = 1 or 2 in both axes; Ho = (H - 1) / s + 1, Wo likewise.
+ *                              x [B][Cin][H][W], y [B][Cout][Ho][Wo], y != x.  w_packed [ksize * ksize taps, kh major][Cin][Cout]
+ *                              (Conv2d.weight permuted (2, 3, 1, 0)).  ch_scale / ch_shift: both or neither; the affine is applied AFTER
+ *                              the sum, as the reference does; relu != 0 clamps last.  Cin, Cout in {32, 64, 128, 256}: an implicit GEMM
+ *                              over K = ksize^2 Cin in exact f32 on v_mfma_f32_32x32x2_f32, the halo tile and the weights of eight input
+ *                              channels at a time in LDS.  Cin = 1 is the stem only (Cout = 32, 3x3, stride 1): nine fmaf per output on
+ *                              the vector unit.  Anything else is SAT_ERR_INVALID before a launch.  B <= 65535.  One fixed summation
+ *                              order, no atomics: the same input gives the same bits.
+ *   sat_se_scale_add_relu_f32  nn.py:65-67 after SELayer.forward's gate (nn.py:31-32): y = relu(z * sigmoid(g[b][c]) + r);
+ *                              z, r, y [B][C][N = H W], g [B][C] = the LOGITS of SELayer.fc (its Sigmoid is applied here); r = the block's
+ *                              input or its 1x1 stride-2 shortcut.  The squeeze (nn.py:30) is sat_row_mean_f32 on
+ *                              [B C][H W] rows, fc's two bias-free Linear layers are sat_linear_rows_f32.
+ *   sat_row_mean_std_f32       MeanStdPooling (pooling.py:33-37), the global context of AttentivePooling (pooling.py:130): per row of
+ *                              x [B][C][T] the mean and the UNBIASED standard deviation over T (torch.std), the deviation summed around
+ *                              the mean in a second pass; out [B][2C], means then deviations.  T < 2 is SAT_ERR_INVALID (torch gives NaN).
+ * The rest of AttentivePooling.forward is sat_linear_rows_f32 (the context's share of the first 1x1 conv, constant over time),
+ * sat_conv1d_f32 (both 1x1 convs), sat_tanh_inplace_f32 and sat_attentive_stats_f32 (pooling.py:134-136) at C = 2560.
+ * ------------------------------------------------------------------------------------------ */
+int sat_conv2d_f32(const float* x, const float* w_packed, float* y, const float* ch_scale, const float* ch_shift, int relu, int B, int Cin,
+                   int Cout, int H, int W, int ksize, int stride, void* stream);
+int sat_se_scale_add_relu_f32(const float* z, const float* gate_logits, const float* r, float* y, int B, int C, int N, void* stream);
+int sat_row_mean_std_f32(const float* x, float* out, int B, int C, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

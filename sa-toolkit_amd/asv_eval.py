@@ -2,7 +2,7 @@
 (reference: egs/anon/vctk/local/eval.py:196-231 -> satools/sidekit/model.py:208-239 `--mode eval` ->
 satools/sidekit/objf.py:186-369 `test` / `compute_metrics` -> satools/sidekit/scoring/__init__.py:7-55 and scoring/metric.py)
 
-`test_metrics` extracts the enrolment and trial x-vectors with the ECAPA-TDNN extractor of this package, `compute_metrics`
+`test_metrics` extracts the enrolment and trial x-vectors with an x-vector extractor of this package (ECAPA-TDNN or the half-ResNet34), `compute_metrics`
 averages the enrolment vectors per speaker, cosine-scores the trial list, applies adaptive s-norm against a cohort and computes
 linkability, min Cllr and the EER.  The arithmetic over vectors runs on the device (csrc/asv_score.hip):
 
@@ -301,7 +301,7 @@ def main(argv=None):
     import argparse
     from .infer_helper import load_model
     ap = argparse.ArgumentParser(prog="asv-eval", description="ASV privacy metrics of a data directory (EER, min Cllr, linkability)")
-    ap.add_argument("checkpoint", help="x-vector checkpoint (final.pt), or synthetic:xvector[?seed=N&speakers=K]")
+    ap.add_argument("checkpoint", help="x-vector checkpoint (final.pt), or synthetic:xvector[?seed=N&speakers=K] / synthetic:xvector_resnet[?seed=N&speakers=K]")
     ap.add_argument("--enrolls-wav-scp", required=True)
     ap.add_argument("--trails-wav-scp", required=True)
     ap.add_argument("--enroll-utt2spk", required=True)

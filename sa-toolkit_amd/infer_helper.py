@@ -22,6 +22,7 @@ _CONFIGS = {
     "local/chain/tuning/tdnnf.py": "tdnnf",                            # the same stacks without the quantiser (the *_aug tags)
     "local/chain/tuning/tdnnf_wav2vec2.py": "tdnnf_wav2vec2",
     "local/tuning/ecapa_tdnn.py": "xvector",          # egs/asv/voxceleb: the ASV x-vector extractor
+    "local/tuning/resnet.py": "xvector_resnet",       # egs/asv/voxceleb: the half-ResNet34 extractor (asv_eval_vox1_resnet)
 }
 
 
@@ -37,6 +38,9 @@ def _builder(base_model_path):
     if kind == "xvector":
         from . import xvector
         return xvector.build
+    if kind == "xvector_resnet":
+        from . import xvector_resnet
+        return xvector_resnet.build
     from . import asrbn
 
     def build(args):

@@ -728,3 +728,60 @@ def segment_mean_l2norm(x, order, offsets):
     seg_dev = torch.empty(U + S + 1, dtype=torch.int32, device=x.device)
     check(lib().sat_segment_mean_l2norm_f32(ptr(x), po, pf, ptr(seg_dev), U, S, D, ptr(out), stream()), "sat_segment_mean_l2norm_f32")
     return out
+
+
+# ---- ResNet x-vector extractor (csrc/conv2d.hip) -------------------------------------------------------
+def pack_conv2d_weight(w, transpose=False):
+    """Conv2d.weight [Cout, Cin, k, k] -> the [k * k, Cin, Cout] layout sat_conv2d_f32 reads (tap-major, output channel contiguous).
+    `transpose` swaps the two kernel axes: the weight of the same conv on images with their two spatial axes swapped"""
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise _lib.SatError(f"pack_conv2d_weight: a float32 [Cout, Cin, k, k] weight is needed, got {w.dtype} {tuple(w.shape)}")
+    if transpose:
+        w = w.transpose(2, 3)
+    cout, cin, k, _ = w.shape
+    return w.permute(2, 3, 1, 0).reshape(k * k, cin, cout).contiguous()
+
+
+def conv2d(x, w_packed, ksize, stride=1, ch_scale=None, ch_shift=None, relu=False):
+    """Conv2d(bias=False, 3x3 with padding 1 or 1x1) + per-channel affine (the BatchNorm in eval) + optional ReLU:
+    x [B, Cin, H, W], w_packed from pack_conv2d_weight -> [B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1]"""
+    x = _f32c(x)
+    if x.dim() != 4 or w_packed.dim() != 3 or w_packed.dtype != torch.float32 or not w_packed.is_contiguous():
+        raise _lib.SatError("conv2d: x [B, Cin, H, W] and packed weights [k * k, Cin, Cout] (pack_conv2d_weight) are needed")
+    B, cin, H, W = x.shape
+    taps, cin_w, cout = w_packed.shape
+    if taps != ksize * ksize or cin_w != cin:
+        raise _lib.SatError(f"conv2d: packed weights {tuple(w_packed.shape)} do not fit x {tuple(x.shape)} with ksize {ksize}")
+    for t in (ch_scale, ch_shift):
+        if t is not None and (t.numel() != cout or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.SatError("conv2d: ch_scale / ch_shift are contiguous f32 vectors of Cout values")
+    stride = int(stride)
+    if stride < 1:
+        raise _lib.SatError("conv2d: stride 1 or 2")
+    y = torch.empty(B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1, dtype=torch.float32, device=x.device)
+    check(lib().sat_conv2d_f32(ptr(x), ptr(w_packed), ptr(y), ptr(ch_scale), ptr(ch_shift), int(bool(relu)), B, cin, cout, H, W, int(ksize),
+                               stride, stream()), "sat_conv2d_f32")
+    return y
+
+
+def se_scale_add_relu(z, gate_logits, r):
+    """relu(z * sigmoid(gate_logits[b, c]) + r): the tail of ResNetBasicBlock.forward; z, r [B, C, ...] of one shape"""
+    z, r = _f32c(z), _f32c(r)
+    if z.dim() < 3 or z.shape != r.shape:
+        raise _lib.SatError(f"se_scale_add_relu: z {tuple(z.shape)} and r {tuple(r.shape)} must be [B, C, ...] of one shape")
+    B, c = z.shape[:2]
+    g = _f32c(gate_logits.reshape(B, c))
+    y = torch.empty_like(z)
+    check(lib().sat_se_scale_add_relu_f32(ptr(z), ptr(g), ptr(r), ptr(y), B, c, z.numel() // (B * c), stream()), "sat_se_scale_add_relu_f32")
+    return y
+
+
+def row_mean_std(x):
+    """[B, C, T] -> [B, 2C]: mean and unbiased standard deviation over time (MeanStdPooling), means first"""
+    x = _f32c(x)
+    if x.dim() != 3:
+        raise _lib.SatError("row_mean_std: [B, C, T]")
+    B, c, t = x.shape
+    out = torch.empty(B, 2 * c, dtype=torch.float32, device=x.device)
+    check(lib().sat_row_mean_std_f32(ptr(x), ptr(out), B, c, t, stream()), "sat_row_mean_std_f32")
+    return out

@@ -176,7 +176,7 @@ def checkpoint(tag, seed=0, conditioning="auto"):
 
 
 def load(spec, option_args=None):
-    """`synthetic:<tag>[?seed=N]` (or `synthetic:xvector[?seed=N&speakers=K]`) -> model with seeded weights (see infer_helper.load_model)"""
+    """`synthetic:<tag>[?seed=N]` (or `synthetic:xvector[?seed=N&speakers=K]` / `synthetic:xvector_resnet[...]`) -> model with seeded weights (see infer_helper.load_model)"""
     from . import infer_helper
     from .anonymizer import SimpleNamespace
     body = spec[len("synthetic:"):]
@@ -193,6 +193,12 @@ def load(spec, option_args=None):
         from . import xvector
         net = xvector.build()(num_speakers=speakers)
         net.load_state_dict(xvector_state(seed, speakers), strict=True)
+        return net
+    if tag == "xvector_resnet":
+        # the half-ResNet34 extractor (egs/asv/voxceleb/local/tuning/resnet.py), 256-dim embeddings
+        from . import xvector_resnet
+        net = xvector_resnet.build()(num_speakers=speakers)
+        net.load_state_dict(xvector_resnet_state(seed, speakers), strict=True)
         return net
     state, net = checkpoint(tag, seed)
     if option_args:
@@ -248,6 +254,31 @@ def xvector_state(seed=0, num_speakers=10):
         elif k.endswith("running_mean"):
             sd[k] = 0.1 * torch.randn(v.shape, generator=g)
         elif ".bn" in k and k.endswith("weight"):
+            sd[k] = 0.8 + 0.4 * torch.rand(v.shape, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.1 * torch.randn(v.shape, generator=g)
+        else:
+            fan_in = v[0].numel() if v.dim() > 1 else v.numel()
+            sd[k] = torch.randn(v.shape, generator=g) * math.sqrt(1.5 / fan_in)
+    return sd
+
+
+def xvector_resnet_state(seed=0, num_speakers=10):
+    """seeded state dict of the ResNet x-vector extractor (reference key names), by the rules of `xvector_state` — except that BatchNorm
+    weights are found by MODULE TYPE: the name test `".bn" in k` misses `shortcut.1` and `attention.2`"""
+    from . import xvector_resnet
+    net = xvector_resnet.build()(num_speakers=num_speakers)
+    bn_weights = {name + ".weight" for name, m in net.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)}
+    sd = {}
+    for i, (k, v) in enumerate(net.state_dict().items()):
+        g = torch.Generator().manual_seed(int(seed) * 100003 + i)
+        if k.endswith("num_batches_tracked") or k.startswith("preprocessor."):
+            sd[k] = v.clone()
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(v.shape, generator=g)
+        elif k.endswith("running_mean"):
+            sd[k] = 0.1 * torch.randn(v.shape, generator=g)
+        elif k in bn_weights:
             sd[k] = 0.8 + 0.4 * torch.rand(v.shape, generator=g)
         elif k.endswith("bias"):
             sd[k] = 0.1 * torch.randn(v.shape, generator=g)

@@ -1,0 +1,229 @@
+"""ASV x-vector extractor (half-ResNet34 with squeeze-excitation) behind the reference's `Net` interface
+(reference: egs/asv/voxceleb/local/tuning/resnet.py:17-79 — the `asv_eval_vox1_resnet` model the anonymization recipe evaluates with):
+`model(wav)` returns `((loss, logits), x_vector)` like the reference's forward with `target=None` — loss = NaN, logits = None, the
+L2-normalised 256-dim embedding — computed on the HIP kernels:
+
+  front end   the ECAPA net's (xvector.py): log-mel + InstanceNorm                    csrc/xvector.hip
+  ResNet      37 Conv2d + BatchNorm2d(eval) (+ ReLU): exact f32 MFMA implicit GEMM      csrc/conv2d.hip  conv2d_mfma_kernel, conv2d_stem_kernel
+              SE squeeze (mean over H x W), its two Linear layers                       row_mean_rows_kernel, linear_rows_kernel
+              relu(out * sigmoid(gate) + shortcut)                                      se_scale_add_relu_kernel
+  pooling     global context: mean / unbiased std over time                             row_mean_std_kernel
+              attention MLP (1x1 Conv1d on the fused conv kernel), tanh                 conv1d, tanh_kernel
+              softmax over time + weighted mean / std at C = 2560                       attentive_stats_kernel
+  head        Linear(5120 -> 256) + BatchNorm, L2 norm                                  linear_rows_kernel, l2norm_rows_kernel
+
+AXES.  The reference runs the ResNet on [B, 1, T, 80] images, frequency innermost (sidekit/archi.py:110-113), and permutes its
+[B, 256, T', 10] output to [B, 2560, T'] for the pooling (sidekit/pooling.py:126-128).  Here TIME stays innermost from the front end's
+[B, 80, T] to the pooling: a 3x3 conv commutes with transposing both the image and the kernel, so `_prepare` packs every 3x3 weight with
+its two kernel axes swapped, and the last layer's [B, 256, 10, T'] output is the pooling's input without a copy.
+
+The parameter tree carries the reference's state-dict keys and shapes, so a reference checkpoint loads with `load_state_dict`.
+No CPU fallback.  An utterance with fewer than two pooled frames (T' < 2: under 9 front-end frames, 1 280 samples) is refused with
+SatError: the reference's global context takes the UNBIASED deviation over T' (torch.std), which is NaN there."""
+import os
+from collections import OrderedDict
+
+import torch
+import torch.nn as nn
+
+from . import _lib, ops, packing
+from .xvector import _ArcMargin, _MelSpecFrontEnd
+
+BLOCKS = (3, 4, 6, 3)
+PLANES = (32, 64, 128, 256)
+
+
+class _SELayer(nn.Module):
+    def __init__(self, channel, reduction=16):
+        super().__init__()
+        self.fc = nn.Sequential(nn.Linear(channel, channel // reduction, bias=False), nn.ReLU(inplace=True),
+                                nn.Linear(channel // reduction, channel, bias=False), nn.Sigmoid())
+
+
+class _BasicBlock(nn.Module):
+    def __init__(self, in_planes, planes, stride, shortcut):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_planes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.se = _SELayer(planes)
+        self.shortcut = nn.Sequential()
+        if shortcut:
+            self.shortcut = nn.Sequential(nn.Conv2d(in_planes, planes, 1, stride=stride, bias=False), nn.BatchNorm2d(planes))
+
+
+class _PreHalfResNet34(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(1, PLANES[0], 3, stride=1, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(PLANES[0])
+        in_planes = PLANES[0]
+        for i, (planes, n) in enumerate(zip(PLANES, BLOCKS)):
+            blocks = []
+            for j in range(n):
+                # the reference's make_layer hands the FIRST block of every layer its stride as a tuple, and ResNetBasicBlock tests
+                # `stride != 1` (sidekit/nn.py:50): true for (1, 1) as well, so layer1's first block has a 1x1 stride-1 shortcut too
+                blocks.append(_BasicBlock(in_planes, planes, 2 if (i > 0 and j == 0) else 1, shortcut=j == 0))
+                in_planes = planes
+            setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
+
+
+class _AttentivePooling(nn.Module):
+    def __init__(self, num_channels, num_freqs=10, attention_channels=128):
+        super().__init__()
+        d = num_channels * num_freqs
+        self.attention = nn.Sequential(nn.Conv1d(3 * d, attention_channels, 1), nn.ReLU(), nn.BatchNorm1d(attention_channels), nn.Tanh(),
+                                       nn.Conv1d(attention_channels, d, 1), nn.Softmax(dim=2))
+
+
+def pooled_frames(frames):
+    """front-end frames -> frames the pooling sees: three stride-2 layers, each (n - 1) // 2 + 1"""
+    for _ in range(3):
+        frames = (frames - 1) // 2 + 1
+    return frames
+
+
+def build(args=None):
+    """same contract as the reference's model-config `build(args)`: returns the Net class"""
+
+    class Net(nn.Module):
+        #: arithmetic of the attention's two 1x1 convs: "f16x3" (split-f16 on the f16 matrix cores) or "f32" (exact f32 MFMA); the 2-D
+        #: convs are exact f32 either way
+        precision = os.environ.get("SATOOLS_AMD_XVECTOR_PRECISION", "f16x3")
+
+        def __init__(self, num_speakers=1):
+            super().__init__()
+            self.preprocessor = _MelSpecFrontEnd()
+            self.sequence_network = _PreHalfResNet34()
+            self.embedding_size = 256
+            self.before_speaker_embedding = nn.Sequential(OrderedDict([
+                ("lin_be", nn.Linear(5120, self.embedding_size, bias=False)), ("bn_be", nn.BatchNorm1d(self.embedding_size))]))
+            self.stat_pooling = _AttentivePooling(256, 10)
+            self.after_speaker_embedding = _ArcMargin(self.embedding_size, num_speakers)
+            self._cache, self._cache_key = None, None
+            super().eval()
+
+        def train(self, mode=True):
+            if mode:
+                raise _lib.SatError("the MI355X x-vector extractor is inference only")
+            return super().train(False)
+
+        # ---- kernel-ready weights ----------------------------------------------------------------
+        def _prepare(self, device):
+            key = (self.precision,) + tuple((p.data_ptr(), p._version, str(p.device)) for p in list(self.parameters()) + list(self.buffers()))
+            if self._cache_key == key:
+                return self._cache
+            _lib.cache_rebuild_begin(device, self._cache is not None)
+            f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+            split = self.precision == "f16x3"
+            pack1 = packing.pack_conv_weight_f16x3 if split else packing.pack_conv_weight
+
+            def bn_affine(bn):
+                s = f32(bn.weight) / torch.sqrt(f32(bn.running_var) + bn.eps)
+                return s.contiguous(), (f32(bn.bias) - f32(bn.running_mean) * s).contiguous()
+
+            def cb(conv, bn):
+                # the kernel axes swapped: this net keeps time innermost, the reference frequency (module docstring)
+                sc, sh = bn_affine(bn)
+                return {"w": ops.pack_conv2d_weight(f32(conv.weight), transpose=True), "k": conv.kernel_size[0], "s": conv.stride[0], "scale": sc, "shift": sh}
+
+            sn = self.sequence_network
+            W = {"stem": cb(sn.conv1, sn.bn1), "blocks": []}
+            for i in range(4):
+                for blk in getattr(sn, f"layer{i + 1}"):
+                    W["blocks"].append({"c1": cb(blk.conv1, blk.bn1), "c2": cb(blk.conv2, blk.bn2),
+                                        "fc0": f32(blk.se.fc[0].weight), "fc2": f32(blk.se.fc[2].weight),
+                                        "sc": cb(blk.shortcut[0], blk.shortcut[1]) if len(blk.shortcut) else None})
+            att = self.stat_pooling.attention
+            d = att[4].weight.shape[0]                                            # 2560
+            w0 = f32(att[0].weight)                                               # [128, 3 d, 1]: frames, context mean, context std
+            sc, sh = bn_affine(att[2])
+            W["att1"] = {"w": pack1(w0[:, :d].contiguous()), "w_ctx": w0[:, d:, 0].contiguous(), "b": f32(att[0].bias), "scale": sc, "shift": sh,
+                         "cout": w0.shape[0]}
+            W["att2"] = {"w": pack1(f32(att[4].weight)), "b": f32(att[4].bias), "cout": d}
+            W["mode1"] = _lib.CONV_F16X3 if split else _lib.CONV_F32
+            sc, sh = bn_affine(self.before_speaker_embedding.bn_be)
+            W["emb"] = {"w": f32(self.before_speaker_embedding.lin_be.weight), "scale": sc, "shift": sh}
+            W["window"] = f32(self.preprocessor.MelSpec.spectrogram.window)
+            W["fb"] = f32(self.preprocessor.MelSpec.mel_scale.fb).t().contiguous()      # [80][513]
+            W["coef"] = float(-self.preprocessor.PreEmphasis.flipped_filter.reshape(-1)[0])
+            self._cache, self._cache_key = W, key
+            _lib.cache_rebuild_end(device)
+            return W
+
+        # ---- forward -----------------------------------------------------------------------------
+        def features(self, x):
+            """[B, n] -> [B, 80, 1 + n // 160]: log-mel front end + InstanceNorm (sidekit/preprocessor.py:223-236)"""
+            W = self._prepare(x.device)
+            return ops.instnorm_rows(ops.melspec_logmel(x, W["window"], W["fb"], W["coef"]))
+
+        @staticmethod
+        def _conv(x, e, relu=False):
+            return ops.conv2d(x, e["w"], e["k"], e["s"], ch_scale=e["scale"], ch_shift=e["shift"], relu=relu)
+
+        def _block(self, x, blk):
+            """ResNetBasicBlock.forward (sidekit/nn.py:57-68) with SELayer.forward (nn.py:23-32)"""
+            out = self._conv(self._conv(x, blk["c1"], relu=True), blk["c2"])
+            B, C = out.shape[:2]
+            m = ops.row_mean(out.view(B, C, -1))                                    # [B, C, 1]
+            g = ops.linear_rows(ops.linear_rows(m, blk["fc0"], relu=True), blk["fc2"])      # the gate's logits
+            r = x if blk["sc"] is None else self._conv(x, blk["sc"])
+            return ops.se_scale_add_relu(out, g, r)
+
+        def resnet(self, feats, taps=None):
+            """[B, 80, T] -> [B, 256, 10, T']; `taps` (a dict) receives the stem's output and each layer's, for the tests"""
+            W = self._prepare(feats.device)
+            x = self._conv(feats.unsqueeze(1), W["stem"], relu=True)
+            if taps is not None:
+                taps["bn1"] = x
+            i = 0
+            for li, n in enumerate(BLOCKS):
+                for _ in range(n):
+                    x = self._block(x, W["blocks"][i])
+                    i += 1
+                if taps is not None:
+                    taps[f"layer{li + 1}"] = x
+            return x
+
+        def pool(self, x, taps=None):
+            """AttentivePooling(256, 10, global_context=True).forward (sidekit/pooling.py:118-138): [B, 2560, T'] -> [B, 5120, 1].
+            The context's 5120 channels are constant over time: their share of the first conv is one matrix-vector product per
+            utterance, added to the frames' 2560 -> 128 product before the ReLU"""
+            W = self._prepare(x.device)
+            B, d, t = x.shape
+            a1, a2 = W["att1"], W["att2"]
+            gc = ops.row_mean_std(x)                                                                # [B, 5120]
+            ctx = ops.linear_rows(gc, a1["w_ctx"], bias=a1["b"])                                    # [B, 128]
+            a = ops.conv1d(x, a1["w"], a1["cout"], 1, res=ctx.unsqueeze(2).expand(B, a1["cout"], t).contiguous(), relu=True, relu_first=True,
+                           ch_scale=a1["scale"], ch_shift=a1["shift"], mode=W["mode1"])
+            logits = ops.conv1d(ops.tanh_(a), a2["w"], a2["cout"], 1, bias=a2["b"], mode=W["mode1"])
+            if taps is not None:
+                taps.update(gc=gc, a=a, logits=logits)
+            return ops.attentive_stats(x, logits)
+
+        def embed(self, feats, taps=None):
+            W = self._prepare(feats.device)
+            B, _, frames = feats.shape
+            if pooled_frames(frames) < 2:
+                raise _lib.SatError(f"x-vector extraction: {frames} frames leave {pooled_frames(frames)} pooled frame; the global context's unbiased "
+                                    "deviation needs two (the reference returns NaN here)")
+            x = self.resnet(feats, taps)
+            pooled = self.pool(x.view(B, x.shape[1] * x.shape[2], x.shape[3]))
+            if taps is not None:
+                taps["pooled"] = pooled
+            e = ops.linear_rows(pooled, W["emb"]["w"], ch_scale=W["emb"]["scale"], ch_shift=W["emb"]["shift"])
+            return ops.l2norm_rows(e.reshape(B, self.embedding_size))
+
+        def forward(self, x, target=None, taps=None):
+            if target is not None:
+                raise _lib.SatError("the MI355X x-vector extractor is inference only (target must be None)")
+            if not x.is_cuda:
+                raise _lib.SatError("x-vector extraction runs on the HIP device only (no CPU fallback)")
+            x = x.to(torch.float32)
+            if x.dim() == 1:
+                x = x.unsqueeze(0)
+            xv = self.embed(self.features(x.contiguous()), taps)
+            return (torch.tensor(float("nan")), None), xv
+
+    return Net
