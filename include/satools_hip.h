@@ -371,7 +371,8 @@ int sat_hifigan_get_option(const sat_hifigan* h, const char* name, int* value);
 int sat_hifigan_set_range_probe(sat_hifigan* h, uint64_t* buf);
 
 /* final stage alone: leaky_relu(0.01) -> ReflectionPad1d((1,0)) -> Conv1d(C,1,7,pad 3) -> tanh
- * (archi.py:87-90).  x [B][C][T] -> y [B][1][T+1];  w [C][7], bias [1]. */
+ * (archi.py:87-90).  x [B][C][T] -> y [B][1][T+1];  w [C][7], bias [1].  C <= 39 (a block keeps a [C][1030] tile of x and the weights in
+ * LDS; more is refused with SAT_ERR_INVALID), T >= 2 (the reflection). */
 int sat_hifigan_convpost_f32(const float* x, const float* w, const float* bias, float* y, int B,
                              int C, int T, void* stream);
 

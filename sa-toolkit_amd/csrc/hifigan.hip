@@ -37,7 +37,7 @@ static void phase_window(int k, int u, int pad, int* dmin, int* dmax) {
 static int g_convpost_quad = 1;
 void convpost_set_quad(int v) { g_convpost_quad = v != 0; }
 constexpr int POST_TILE = 1024;
-constexpr int POST_MAXC = 64;
+constexpr int POST_MAXC = 160 * 1024 / ((POST_TILE + 6 + 7) * 4);  // 39: the [C][1024+6] tile and the [C][7] weights fit the 160 KiB of LDS
 
 template <int C, bool QUAD = false>
 __global__ void __launch_bounds__(256) convpost_kernel(const float* __restrict__ x,
