@@ -182,12 +182,22 @@ _PROTOS = {
     "sat_row_mean_std_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# include/satools_hip_stats.h (csrc/stats/): a second table, bound like the first one
+_PROTOS_STATS = {
+    "sat_eer_bootstrap_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
 def exported_symbols():
     """names declared in include/satools_hip.h that the library must export"""
     return sorted(_PROTOS)
+
+
+def stats_symbols():
+    """names declared in include/satools_hip_stats.h that the library must export"""
+    return sorted(_PROTOS_STATS)
 
 
 def library_path():
@@ -204,7 +214,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python sa-toolkit_amd/build.py` "
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

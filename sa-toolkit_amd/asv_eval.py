@@ -18,7 +18,9 @@ order, the monotonicity ramp), with a linear-time stack PAV in place of the refe
 
 EER: the reference takes `eer`, its bootstrap interval and the threshold from the third-party `feerci` package.  When `feerci` can be
 imported it is called exactly as objf.py:332 calls it; otherwise `eer` is the ROCCH-EER x 100, `eer_threshold` the calibrated LLR of
-the ROCCH segment that crosses the diagonal, and `eer_lower` / `eer_upper` are None (parity unpinned: INTEGRATION.md)."""
+the ROCCH segment that crosses the diagonal, and `eer_lower` / `eer_upper` are None (parity unpinned: INTEGRATION.md).  With
+`eer_ci` (`asv-eval --eer-ci M`) the three come from `eer_interval` instead: the empirical EER of the calibrated LLRs and the percentile
+interval of M bootstrap replicates of it, drawn and counted on the device (ops.eer_bootstrap, csrc/stats/eer_bootstrap.hip)."""
 import json
 import os
 
@@ -152,8 +154,70 @@ def min_cllr(tar, non, monotonicity_epsilon=1e-6):
     return cllr(c["tar_llrs"], c["non_llrs"]), c["eer"], c["tar_llrs"], c["non_llrs"]
 
 
-def score_metrics(mated, non_mated):
-    """the reference's metric set of one pair of score sets (objf.py:330-339) -> (dict, calibrated mated, calibrated non-mated)"""
+# ---- the empirical EER and its bootstrap interval ------------------------------------------------------------------
+def eer_cuts(tar_sorted, non_sorted):
+    """the two sorted score sets as integer cut tables over the K distinct values v_0 < ... < v_{K-1} of both together, +inf as index K:
+    cut_tar[k] = #{tar < v_k}, cut_non[k] = #{non < v_k}, cut_*[K] = n_* -> (cut_tar [K + 1], cut_non [K + 1]) int32.
+    The EER depends on the sets through these tables alone."""
+    tar = np.asarray(tar_sorted, dtype=np.float64)
+    non = np.asarray(non_sorted, dtype=np.float64)
+    if tar.ndim != 1 or non.ndim != 1 or tar.size == 0 or non.size == 0:
+        raise ValueError("eer_cuts: two non-empty score vectors are needed")
+    if np.isnan(tar).any() or np.isnan(non).any():
+        raise ValueError("eer_cuts: NaN scores have no order")
+    if np.any(np.diff(tar) < 0) or np.any(np.diff(non) < 0):
+        raise ValueError("eer_cuts: the score vectors must be sorted")
+    v = np.unique(np.concatenate([tar, non]))
+    cut_tar = np.append(np.searchsorted(tar, v, side="left"), tar.size).astype(np.int32)
+    cut_non = np.append(np.searchsorted(non, v, side="left"), non.size).astype(np.int32)
+    return cut_tar, cut_non
+
+
+def _eer_from_cuts(cut_tar, cut_non):
+    n_tar, n_non = int(cut_tar[-1]), int(cut_non[-1])
+    miss = cut_tar.astype(np.int64)
+    fa = n_non - cut_non.astype(np.int64)
+    k = int(np.argmax(miss * n_non >= fa * n_tar))            # the first threshold at which the misses have caught up: 1 <= k <= K
+    m, f = int(miss[k]), int(fa[k - 1])
+    return min(m / n_tar, f / n_non), m, f
+
+
+def empirical_eer(tar, non):
+    """the equal error rate of the two score sets as they are, no convex hull -> (eer, miss_count, fa_count).
+    A trial is accepted when score >= t; t runs over the K distinct values of both sets and +inf (index K).  miss(k) = #{tar < v_k} never
+    decreases, fa(k) = #{non >= v_k} never increases, miss(0) = 0 and fa(K) = 0.  With k* the smallest k at which miss(k) n_non >=
+    fa(k) n_tar (int64 products: no rounding decides it),  EER = min(miss(k*) / n_tar, fa(k* - 1) / n_non) = min_t max(P_miss(t), P_fa(t)).
+    Thresholds sit on distinct values, so ties are safe.  Never smaller than the ROCCH-EER of `calibrate`."""
+    ct, cn = eer_cuts(np.sort(np.asarray(tar, dtype=np.float64)), np.sort(np.asarray(non, dtype=np.float64)))
+    return _eer_from_cuts(ct, cn)
+
+
+def eer_interval(tar, non, m=10000, ci=0.95, seed=0, device=None):
+    """the empirical EER and the percentile interval of m bootstrap replicates of it -> (eer, lower, upper, replicate_eers [m]), fractions.
+    Replicate r resamples both sets with replacement (ops.eer_bootstrap: Philox4x32-10 draws, a function of (seed, r) alone; the index
+    mapping (u n) >> 32 is biased by at most n / 2^32 relative between two indices, 2.4e-4 at n = 2^20) and the device returns its two
+    integer counts; the two divisions and the min are float64 here.  lower / upper = np.percentile(replicates, [50 (1 - ci), 50 (1 + ci)])
+    with numpy's default linear rule.  feerci's own percentile and tie rules are not known here: parity with feerci stays unpinned."""
+    if not 0 < ci < 1:
+        raise ValueError(f"eer_interval: ci = {ci} outside (0, 1)")
+    tar = np.sort(np.asarray(tar, dtype=np.float64))
+    non = np.sort(np.asarray(non, dtype=np.float64))
+    ct, cn = eer_cuts(tar, non)
+    eer = _eer_from_cuts(ct, cn)[0]
+    miss, fa = ops.eer_bootstrap(ct, cn, tar.size, non.size, m, seed=seed, device=device)
+    reps = np.minimum(miss.cpu().numpy().astype(np.float64) / tar.size, fa.cpu().numpy().astype(np.float64) / non.size)
+    # 50 (1 -+ ci) as 50 -+ 50 ci: 1 - 0.95 is not 0.05 in float64 (50 (1 - 0.95) = 2.500000000000002, and the interpolated percentile moves
+    # by an ulp), while 50 - 50 * 0.95 is 2.5
+    lower, upper = np.percentile(reps, [50 - 50 * ci, 50 + 50 * ci])
+    return eer, float(lower), float(upper), reps
+
+
+def score_metrics(mated, non_mated, eer_ci=None):
+    """the reference's metric set of one pair of score sets (objf.py:330-339) -> (dict, calibrated mated, calibrated non-mated).
+    eer_ci = dict(m=replicates, ci=0.95, seed=0[, device]): without feerci, `eer`, `eer_lower` and `eer_upper` (x 100) come from
+    `eer_interval` of the calibrated LLRs, the arguments the reference hands to feerci.  The reference takes all three from one routine, so
+    `eer` is then the EMPIRICAL EER, not the ROCCH-EER (which is never larger).  `eer_threshold` and the key set do not change, and
+    feerci, when it can be imported, still wins."""
     d_sys = linkability(mated, non_mated)[0]
     c = calibrate(mated, non_mated)
     cmin = cllr(c["tar_llrs"], c["non_llrs"])
@@ -161,6 +225,9 @@ def score_metrics(mated, non_mated):
         from feerci import feerci
     except ImportError:
         eer, lower, upper, thr = c["eer"] * 100, None, None, c["eer_threshold"]
+        if eer_ci is not None:
+            e, lo, up, _ = eer_interval(c["tar_llrs"], c["non_llrs"], **eer_ci)
+            eer, lower, upper = e * 100, lo * 100, up * 100
     else:
         eer, lower, upper, _boot, thr = feerci(c["non_llrs"], c["tar_llrs"], is_sorted=False, return_threshold=True)
         eer, lower, upper, thr = float(eer * 100), float(lower * 100), float(upper * 100), float(thr)
@@ -234,12 +301,14 @@ def score_trials(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, spk_of_trial, 
     return score.cpu().numpy(), score_as.cpu().numpy()
 
 
-def compute_metrics(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, trials_file, out_scores, cohort=None, device=None):
+def compute_metrics(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, trials_file, out_scores, cohort=None, device=None, eer_ci=None):
     """objf.py:268-369: x-vectors by utterance, the enrolment speakers' utterance lists, the trial list -> the metric dict
     (`linkability`, `eer`, `eer_lower`, `eer_upper`, `min_cllr`, `eer_threshold`, `asnorm` = the same six after adaptive s-norm
     against `cohort` (None without one), `score` = the calibrated (mated, non-mated) LLRs of the last set computed).
-    Writes `<out_scores>/scores`: `enrol test score` per trial."""
+    Writes `<out_scores>/scores`: `enrol test score` per trial.  eer_ci: see `score_metrics`."""
     spk, utt, lab = read_trials(trials_file)
+    if eer_ci is not None and "device" not in eer_ci:
+        eer_ci = dict(eer_ci, device=device)
     score, score_as = score_trials(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, spk, utt, cohort=cohort, device=device)
     os.makedirs(out_scores, exist_ok=True)
     with open(os.path.join(out_scores, "scores"), "w") as f:
@@ -249,19 +318,20 @@ def compute_metrics(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, trials_file
     tar, non = lab == "target", lab == "nontarget"
     if not tar.any() or not non.any():
         raise _lib.SatError(f"{trials_file}: the metrics need target and nontarget trials")
-    metrics, mated, non_mated = score_metrics(score[tar].astype(np.float64), score[non].astype(np.float64))
+    metrics, mated, non_mated = score_metrics(score[tar].astype(np.float64), score[non].astype(np.float64), eer_ci=eer_ci)
     metrics["asnorm"] = {k: None for k in ("eer", "linkability", "eer_lower", "eer_upper", "min_cllr", "eer_threshold")}
     if score_as is not None:
-        m_as, mated, non_mated = score_metrics(score_as[tar].astype(np.float64), score_as[non].astype(np.float64))
+        m_as, mated, non_mated = score_metrics(score_as[tar].astype(np.float64), score_as[non].astype(np.float64), eer_ci=eer_ci)
         metrics["asnorm"].update(m_as)
     metrics["score"] = (mated, non_mated)
     return metrics
 
 
-def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_file, out_dir, as_norm=True):
+def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_file, out_dir, as_norm=True, eer_ci=None):
     """objf.py:189-266: extract, score, measure.  Writes `<out_dir>/xvectors.npz` (`utts`, `xvectors`), `scores` and `metric.json`
     and returns the metric dict.  One utterance per extractor call, as the reference (the kernels take no per-utterance lengths,
-    and zero padding would change the InstanceNorm and the pooling); an utterance of both lists is extracted once."""
+    and zero padding would change the InstanceNorm and the pooling); an utterance of both lists is extracted once.
+    eer_ci: see `score_metrics`."""
     from .pipeline import load_wav_from_scp, read_wav_scp
     model.eval()
     device = next(model.parameters()).device
@@ -288,13 +358,26 @@ def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_f
     both.update(trial)
     np.savez(os.path.join(out_dir, "xvectors.npz"), utts=np.asarray(list(both)),
              xvectors=torch.stack(list(both.values())).cpu().numpy())
-    metrics = compute_metrics(enroll, trial, spk2utt, trials_file, out_dir, cohort=cohort, device=device)
+    metrics = compute_metrics(enroll, trial, spk2utt, trials_file, out_dir, cohort=cohort, device=device, eer_ci=eer_ci)
     with open(os.path.join(out_dir, "metric.json"), "w") as f:
         json.dump({k: v for k, v in metrics.items() if k != "score"}, f, indent=1)
     return metrics
 
 
 test_metrics.__test__ = False      # (a library function, not a pytest case)
+
+
+def report_lines(metrics):
+    """the two lines of the reference's report step (eval.py:87-96 print_asv_metrics) from a metric dict: raw scores, then adaptive s-norm
+    (left out when there was no cohort).  The half-width (upper - lower) / 2 of the interval, to 3 places, follows the EER when there is
+    an interval and is omitted when `eer_lower` / `eer_upper` are None."""
+    out = []
+    for m in (metrics, metrics.get("asnorm") or {}):
+        if m.get("eer") is None:
+            continue
+        pm = "" if m.get("eer_lower") is None or m.get("eer_upper") is None else f" ± {round((m['eer_upper'] - m['eer_lower']) / 2, 3)}"
+        out.append(f" %EER: {round(m['eer'], 3)}{pm}, Min Cllr: {round(m['min_cllr'], 3)}, linkability: {round(m['linkability'], 3)}")
+    return out
 
 
 def main(argv=None):
@@ -309,7 +392,16 @@ def main(argv=None):
     ap.add_argument("--decode-output", required=True, help="directory for xvectors.npz, scores and metric.json")
     ap.add_argument("--no-as-norm", action="store_true", help="skip adaptive s-norm")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--eer-ci", type=int, default=0, metavar="M",
+                    help="bootstrap replicates for the 95 %% interval of the EER (eer_lower / eer_upper; eer becomes the empirical EER); 0 = off")
+    ap.add_argument("--eer-ci-seed", type=int, default=0, metavar="S", help="seed of the bootstrap draws")
+    ap.add_argument("--report", action="store_true", help="also print the two lines of the reference's report step (raw, AS-norm)")
     a = ap.parse_args(argv)
+    if a.eer_ci < 0:
+        ap.error("--eer-ci takes a count of replicates (0 = off)")
     model = load_model(a.checkpoint).to(a.device)
-    m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm)
+    ci = dict(m=a.eer_ci, ci=0.95, seed=a.eer_ci_seed) if a.eer_ci else None
+    m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm, eer_ci=ci)
     print(json.dumps({k: v for k, v in m.items() if k != "score"}))
+    if a.report:
+        print("\n".join(report_lines(m)))

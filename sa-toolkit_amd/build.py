@@ -12,14 +12,28 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 
 def sources():
-    return sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")))
+    """the kernels directly in csrc/ (include/satools_hip.h) and those of csrc/stats/ (include/satools_hip_stats.h): one library"""
+    return sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip"))) + sorted(glob.glob(os.path.join(HERE, "csrc", "stats", "*.hip")))
+
+
+def headers():
+    """what every object depends on besides its own source"""
+    inc = os.path.join(HERE, "..", "include")
+    return (glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "stats", "*.h"))
+            + [os.path.join(inc, "satools_hip.h"), os.path.join(inc, "satools_hip_stats.h")])
+
+
+def object_name(src):
+    """csrc/x.hip -> x.hip.o, csrc/stats/x.hip -> stats_x.hip.o: a file name may repeat between the two directories"""
+    rel = os.path.relpath(src, os.path.join(HERE, "csrc"))
+    return rel.replace(os.sep, "_") + ".o"
 
 
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(HERE, "csrc", "*.h")) + [os.path.join(HERE, "..", "include", "satools_hip.h")]
+    deps = sources() + headers()
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -31,9 +45,9 @@ def build(force=False, verbose=True, jobs=None):
     jobs = jobs or min(4, os.cpu_count() or 1)
     procs, objs = [], []
     for src in sources():
-        obj = os.path.join(objdir, os.path.basename(src) + ".o")
+        obj = os.path.join(objdir, object_name(src))
         objs.append(obj)
-        hdrs = glob.glob(os.path.join(HERE, "csrc", "*.h")) + [os.path.join(HERE, "..", "include", "satools_hip.h")]
+        hdrs = headers()
         if not force and os.path.exists(obj) and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in [src] + hdrs):
             continue
         cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]

@@ -730,6 +730,70 @@ def segment_mean_l2norm(x, order, offsets):
     return out
 
 
+# ---- resampling statistics (csrc/stats/eer_bootstrap.hip, include/satools_hip_stats.h) -----------------
+EER_BOOTSTRAP_MAX_SIDE = 1 << 20      # SAT_EER_BOOTSTRAP_MAX_SIDE
+
+
+def _cut_table(v, n, what):
+    """a cut table (host array, CPU or device tensor) -> (int32 numpy copy for the checks, the device tensor it came from or None)"""
+    import numpy as np
+    dev = None
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            dev = v
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v)
+    if a.ndim != 1 or a.size < 2 or a.dtype.kind not in "iu":
+        raise _lib.SatError(f"{what}: a one-dimensional integer table of K + 1 >= 2 values is needed, got {a.dtype} {a.shape}")
+    if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+        raise _lib.SatError(f"{what}: values do not fit 32 bits")
+    if np.any(np.diff(a.astype(np.int64)) < 0):
+        raise _lib.SatError(f"{what}: the counts must not decrease")
+    if a[0] < 0 or a[-1] != n:
+        raise _lib.SatError(f"{what}: the table must run from a count >= 0 to n = {n}, got {int(a[0])} .. {int(a[-1])}")
+    if dev is not None and (dev.dtype != torch.int32 or not dev.is_contiguous()):
+        dev = None                    # (uploaded again below, as int32)
+    return np.ascontiguousarray(a, dtype=np.int32), dev
+
+
+def eer_bootstrap(cut_tar, cut_non, n_tar, n_non, m, seed=0, first_replicate=0, device=None):
+    """bootstrap replicates first_replicate .. first_replicate + m - 1 of the empirical EER of two score sets given as their cut tables
+    (asv_eval.eer_cuts; include/satools_hip_stats.h) -> (miss_at [m], fa_before [m]) int32 device tensors: the replicate's EER is
+    min(miss_at / n_tar, fa_before / n_non).  Draws: Philox4x32-10 at the counter (j >> 2, replicate, stream, 0) under the key `seed`,
+    word j & 3, mapped to an index by (u n) >> 32 — two indices differ in probability by at most n / 2^32 relative (2.4e-4 at the
+    largest n, 2^20).  A replicate depends on (seed, its number) alone.  The tables may be host arrays or device tensors; they are checked
+    on the host before the launch (K + 1 values of int32 range, non-decreasing, ending in n, one side starting at 0)."""
+    n_tar, n_non, m, seed, first_replicate = int(n_tar), int(n_non), int(m), int(seed), int(first_replicate)
+    if n_tar < 1 or n_non < 1 or m < 1:
+        raise _lib.SatError(f"eer_bootstrap: n_tar = {n_tar}, n_non = {n_non}, m = {m} must all be at least 1")
+    if max(n_tar, n_non) > EER_BOOTSTRAP_MAX_SIDE:
+        raise _lib.SatError(f"eer_bootstrap: n_tar = {n_tar}, n_non = {n_non}: a side holds at most {EER_BOOTSTRAP_MAX_SIDE} trials")
+    if not 0 <= seed < 2 ** 64:
+        raise _lib.SatError(f"eer_bootstrap: seed = {seed} is not a 64-bit unsigned value")
+    if first_replicate < 0 or first_replicate + m > 2 ** 31 - 1:
+        raise _lib.SatError(f"eer_bootstrap: replicates {first_replicate} .. {first_replicate + m - 1} do not fit 0 .. 2^31 - 1")
+    ct, dt = _cut_table(cut_tar, n_tar, "eer_bootstrap: cut_tar")
+    cn, dn = _cut_table(cut_non, n_non, "eer_bootstrap: cut_non")
+    K = ct.size - 1
+    if cn.size != ct.size or K > n_tar + n_non:
+        raise _lib.SatError(f"eer_bootstrap: {ct.size} and {cn.size} table entries do not fit K + 1 with K <= n_tar + n_non = {n_tar + n_non}")
+    if ct[0] != 0 and cn[0] != 0:
+        raise _lib.SatError("eer_bootstrap: no score lies below the smallest threshold: a table must start at 0")
+    if device is None:
+        device = dt.device if dt is not None else dn.device if dn is not None else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.SatError("eer_bootstrap: the replicates are drawn on the HIP device only (no CPU fallback)")
+    dt = dt.to(device) if dt is not None else torch.from_numpy(ct).to(device)
+    dn = dn.to(device) if dn is not None else torch.from_numpy(cn).to(device)
+    miss_at = torch.empty(m, dtype=torch.int32, device=device)
+    fa_before = torch.empty(m, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        check(lib().sat_eer_bootstrap_i32(ptr(dt), ptr(dn), K, n_tar, n_non, first_replicate, m, seed, ptr(miss_at), ptr(fa_before), stream()),
+              "sat_eer_bootstrap_i32")
+    return miss_at, fa_before
+
+
 # ---- ResNet x-vector extractor (csrc/conv2d.hip) -------------------------------------------------------
 def pack_conv2d_weight(w, transpose=False):
     """Conv2d.weight [Cout, Cin, k, k] -> the [k * k, Cin, Cout] layout sat_conv2d_f32 reads (tap-major, output channel contiguous).
