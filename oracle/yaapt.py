@@ -189,17 +189,24 @@ def dynamic5(pitch, merit, k1, f0_min):
     return pitch[path, torch.arange(T)]
 
 
-def spec_track(filt2, energy, vuv, plan, aux=None):
-    """yaapt.py:184-312 -> (spec_pitch [nframes], pitch_std)"""
-    p = plan.p
+def spec_candidates(filt2, vuv, plan):
+    """yaapt.py:184-238: SHC and peaks() of every frame above the NLFER threshold -> (cand_pitch, cand_merit) [4, nframes];
+    the other frames keep the defaults (pitch 0, merit 1)"""
     nf = plan.nframes
     cand_pitch = torch.zeros((plan.maxpeaks, nf))
     cand_merit = torch.ones((plan.maxpeaks, nf))
     frames, shc = shc_frames(filt2, vuv, plan)
     for i, f in enumerate(frames.tolist()):
         cand_pitch[:, f], cand_merit[:, f] = peaks(shc[i], plan)
-    if aux is not None:
-        aux.update(cand_pitch=cand_pitch.clone(), cand_merit=cand_merit.clone())
+    return cand_pitch, cand_merit
+
+
+def spec_select(cand_pitch, cand_merit, plan):
+    """yaapt.py:241-312: selection, smoothing, Viterbi and interpolation of the candidates -> (spec_pitch [nframes],
+    pitch_std).  Raises like the reference when no frame has a candidate: its medfilt of an empty tensor fails inside
+    unfold (:256 -> :54-69), before the `num_voiced_cand > 0` branches further down can be reached."""
+    p = plan.p
+    nf = plan.nframes
     spec_pitch = cand_pitch[0, :].clone()
     voiced = cand_pitch[0, :] > 0.0
     vcp, vcm = cand_pitch[:, voiced].clone(), cand_merit[:, voiced].clone()
@@ -210,7 +217,7 @@ def spec_track(filt2, energy, vuv, plan, aux=None):
     ar = torch.arange(nv)
     pk, mr = vcp[index, ar], vcm[index, ar]
     med_k = max(1, int(p["median_value"]) - 2)
-    pk = medfilt(pk, med_k) if nv > 0 else pk
+    pk = medfilt(pk, med_k)
     vcp[index, ar] = pk
     vcm[index, ar] = mr
     wtrans = p["dp5_k1"] * std_v / avg_v
@@ -237,10 +244,19 @@ def spec_track(filt2, energy, vuv, plan, aux=None):
     return spec_pitch, pitch_std
 
 
-def frame_means(filt, plan):
+def spec_track(filt2, energy, vuv, plan, aux=None):
+    """yaapt.py:184-312 -> (spec_pitch [nframes], pitch_std)"""
+    cand_pitch, cand_merit = spec_candidates(filt2, vuv, plan)
+    if aux is not None:
+        aux.update(cand_pitch=cand_pitch.clone(), cand_merit=cand_merit.clone())
+    return spec_select(cand_pitch, cand_merit, plan)
+
+
+def frame_means(filt, plan, means=None):
     """time_track subtracts each 400-sample frame's mean IN PLACE on overlapping views
     (yaapt.py:711-714 + crs_corr :589): frame k's first 80 samples already carry frame k-1's
-    subtraction.  Returns the de-meaned frames [nframes, 400] exactly as crs_corr sees them."""
+    subtraction.  Returns the de-meaned frames [nframes, 400] exactly as crs_corr sees them; the means themselves are
+    appended to the list `means`, if given."""
     T, n, hop = plan.tda_nframes, plan.tda_len, plan.frame_jump
     ov = n - hop
     out = torch.empty(T, n)
@@ -252,6 +268,8 @@ def frame_means(filt, plan):
         m = torch.mean(cur)
         out[k] = cur - m
         prev_mean = m
+        if means is not None:
+            means.append(m)
     return out
 
 
@@ -382,6 +400,8 @@ def yaapt_one(x, opts, aux=None, biquad_order="torchaudio", biquad_iir="torchaud
     filt = bl(sig)
     filt2 = bl(sig ** 2)
     energy, vuv = nlfer(filt, plan)
+    if aux is not None:       # filled stage by stage: a raising utterance leaves what was computed before it
+        aux.update(filt=filt, filt2=filt2, energy=energy, vuv=vuv)
     spec_pitch, pitch_std = spec_track(filt2, energy, vuv, plan, aux=aux)
     tp1, tm1 = time_track(filt, spec_pitch, pitch_std, plan)
     tp2, tm2 = time_track(filt2, spec_pitch, pitch_std, plan)
