@@ -187,6 +187,11 @@ _PROTOS_STATS = {
     "sat_eer_bootstrap_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/satools_hip_conv2d16.h (csrc/conv2d16/): a third table, bound like the other two
+_PROTOS_CONV2D16 = {
+    "sat_conv2d_f16x3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -198,6 +203,11 @@ def exported_symbols():
 def stats_symbols():
     """names declared in include/satools_hip_stats.h that the library must export"""
     return sorted(_PROTOS_STATS)
+
+
+def conv2d16_symbols():
+    """names declared in include/satools_hip_conv2d16.h that the library must export"""
+    return sorted(_PROTOS_CONV2D16)
 
 
 def library_path():
@@ -214,7 +224,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python sa-toolkit_amd/build.py` "
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

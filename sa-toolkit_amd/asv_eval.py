@@ -396,10 +396,16 @@ def main(argv=None):
                     help="bootstrap replicates for the 95 %% interval of the EER (eer_lower / eer_upper; eer becomes the empirical EER); 0 = off")
     ap.add_argument("--eer-ci-seed", type=int, default=0, metavar="S", help="seed of the bootstrap draws")
     ap.add_argument("--report", action="store_true", help="also print the two lines of the reference's report step (raw, AS-norm)")
+    ap.add_argument("--resnet-conv2d", choices=("f32", "f16x3"), default=None,
+                    help="arithmetic of the 2-D convs of the ResNet extractor's blocks (its conv2d_precision); an error for the ECAPA model")
     a = ap.parse_args(argv)
     if a.eer_ci < 0:
         ap.error("--eer-ci takes a count of replicates (0 = off)")
     model = load_model(a.checkpoint).to(a.device)
+    if a.resnet_conv2d is not None:
+        if not hasattr(model, "conv2d_precision"):
+            ap.error("--resnet-conv2d: the loaded model is not the ResNet extractor (it has no 2-D convs)")
+        model.conv2d_precision = a.resnet_conv2d
     ci = dict(m=a.eer_ci, ci=0.95, seed=a.eer_ci_seed) if a.eer_ci else None
     m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm, eer_ci=ci)
     print(json.dumps({k: v for k, v in m.items() if k != "score"}))

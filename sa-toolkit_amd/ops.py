@@ -828,6 +828,56 @@ def conv2d(x, w_packed, ksize, stride=1, ch_scale=None, ch_shift=None, relu=Fals
     return y
 
 
+def pack_conv2d_weight_f16x3(w, transpose=False):
+    """Conv2d.weight [Cout, Cin, k, k] float32 -> (w_split, descale) for sat_conv2d_f16x3_f32 (include/satools_hip_conv2d16.h):
+    w_split = f16 [Cin / 16, k * k, 2 (hi | lo), 2 (channel half), Cout, 8] of w' = w * 2^e — hi = f16(w'), lo = f16(w' - hi) — with the
+    per-layer scale of packing.pack_conv_weight_f16x3 (the largest |w'| in [2^9, 2^10); e = 0 for an all-zero weight), descale = 2^-e.
+    `transpose` swaps the two kernel axes, as in pack_conv2d_weight.  Non-finite weights raise packing.SplitRangeError"""
+    from . import packing
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise _lib.SatError(f"pack_conv2d_weight_f16x3: a float32 [Cout, Cin, k, k] weight is needed, got {w.dtype} {tuple(w.shape)}")
+    if w.shape[1] % 16 != 0:
+        raise _lib.SatError(f"pack_conv2d_weight_f16x3: Cin = {w.shape[1]} is not a multiple of 16")
+    if transpose:
+        w = w.transpose(2, 3)
+    e = packing.f16x3_scale_exponent(w)
+    cout, cin, k, _ = w.shape
+    p = w.detach() * float(2.0 ** e)                                              # (a power of two: exact)
+    p = p.reshape(cout, cin // 16, 2, 8, k * k).permute(1, 4, 2, 0, 3).contiguous()      # [chunk][tap][half][co][8]
+    hi = p.to(torch.float16)
+    lo = (p - hi.to(torch.float32)).to(torch.float16)
+    return torch.stack([hi, lo], dim=2).contiguous(), float(2.0 ** -e)
+
+
+def conv2d_f16x3(x, w_split, descale, ksize, stride=1, ch_scale=None, ch_shift=None, relu=False, overflow=None):
+    """conv2d in split-f16 arithmetic (three f16 MFMA products per term, f32 accumulation): x [B, Cin, H, W] f32, (w_split, descale) from
+    pack_conv2d_weight_f16x3 -> [B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1] f32.  `overflow`: an int32 tensor of one element
+    on x's device, or None; the kernel makes it nonzero if a staged activation had |x| >= 65 520 or was not finite (the results are then
+    unspecified), and never clears it"""
+    x = _f32c(x)
+    if x.dim() != 4 or w_split.dim() != 6 or w_split.dtype != torch.float16 or not w_split.is_contiguous():
+        raise _lib.SatError("conv2d_f16x3: x [B, Cin, H, W] and split weights f16 [Cin / 16, k * k, 2, 2, Cout, 8] (pack_conv2d_weight_f16x3) are needed")
+    B, cin, H, W = x.shape
+    chunks, taps, parts, halves, cout, eight = w_split.shape
+    if taps != ksize * ksize or chunks * 16 != cin or (parts, halves, eight) != (2, 2, 8):
+        raise _lib.SatError(f"conv2d_f16x3: split weights {tuple(w_split.shape)} do not fit x {tuple(x.shape)} with ksize {ksize}")
+    for t in (ch_scale, ch_shift):
+        if t is not None and (t.numel() != cout or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.SatError("conv2d_f16x3: ch_scale / ch_shift are contiguous f32 vectors of Cout values")
+    stride = int(stride)
+    if stride < 1:
+        raise _lib.SatError("conv2d_f16x3: stride 1 or 2")
+    descale = float(descale)
+    if not (0.0 < descale < float("inf")):
+        raise _lib.SatError(f"conv2d_f16x3: descale = {descale} (the 2^-e pack_conv2d_weight_f16x3 returned)")
+    if overflow is not None and (overflow.dtype != torch.int32 or overflow.numel() != 1 or overflow.device != x.device):
+        raise _lib.SatError("conv2d_f16x3: overflow is one int32 on x's device")
+    y = torch.empty(B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1, dtype=torch.float32, device=x.device)
+    check(lib().sat_conv2d_f16x3_f32(ptr(x), ptr(w_split), descale, ptr(y), ptr(ch_scale), ptr(ch_shift), int(bool(relu)), B, cin, cout, H, W,
+                                     int(ksize), stride, ptr(overflow), stream()), "sat_conv2d_f16x3_f32")
+    return y
+
+
 def se_scale_add_relu(z, gate_logits, r):
     """relu(z * sigmoid(gate_logits[b, c]) + r): the tail of ResNetBasicBlock.forward; z, r [B, C, ...] of one shape"""
     z, r = _f32c(z), _f32c(r)

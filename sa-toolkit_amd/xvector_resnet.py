@@ -5,6 +5,8 @@ L2-normalised 256-dim embedding — computed on the HIP kernels:
 
   front end   the ECAPA net's (xvector.py): log-mel + InstanceNorm                    csrc/xvector.hip
   ResNet      37 Conv2d + BatchNorm2d(eval) (+ ReLU): exact f32 MFMA implicit GEMM      csrc/conv2d.hip  conv2d_mfma_kernel, conv2d_stem_kernel
+              opt-in (`conv2d_precision = "f16x3"`): the 36 convs of the blocks in        csrc/conv2d16/   conv2d_f16x3_kernel
+              split-f16 arithmetic, exact f32 again for a batch that leaves the f16 range
               SE squeeze (mean over H x W), its two Linear layers                       row_mean_rows_kernel, linear_rows_kernel
               relu(out * sigmoid(gate) + shortcut)                                      se_scale_add_relu_kernel
   pooling     global context: mean / unbiased std over time                             row_mean_std_kernel
@@ -89,8 +91,15 @@ def build(args=None):
 
     class Net(nn.Module):
         #: arithmetic of the attention's two 1x1 convs: "f16x3" (split-f16 on the f16 matrix cores) or "f32" (exact f32 MFMA); the 2-D
-        #: convs are exact f32 either way
+        #: convs are governed by `conv2d_precision` alone
         precision = os.environ.get("SATOOLS_AMD_XVECTOR_PRECISION", "f16x3")
+        #: arithmetic of the 2-D convs of the residual blocks (3x3 and 1x1 shortcuts): "f32" (exact f32 MFMA, the default) or "f16x3"
+        #: (split-f16, csrc/conv2d16/).  The stem is exact f32 either way.  A batch with an activation outside the f16 range
+        #: (|x| >= 65 520 or non-finite) is run again in "f32": `split_fallbacks` counts those, `last_conv2d_arithmetic` names what the
+        #: last batch's result came from
+        conv2d_precision = os.environ.get("SATOOLS_AMD_RESNET_CONV2D", "f32")
+        split_fallbacks = 0
+        last_conv2d_arithmetic = None
 
         def __init__(self, num_speakers=1):
             super().__init__()
@@ -111,7 +120,9 @@ def build(args=None):
 
         # ---- kernel-ready weights ----------------------------------------------------------------
         def _prepare(self, device):
-            key = (self.precision,) + tuple((p.data_ptr(), p._version, str(p.device)) for p in list(self.parameters()) + list(self.buffers()))
+            if self.conv2d_precision not in ("f32", "f16x3"):
+                raise _lib.SatError(f"conv2d_precision = {self.conv2d_precision!r}: \"f32\" or \"f16x3\"")
+            key = (self.precision, self.conv2d_precision) + tuple((p.data_ptr(), p._version, str(p.device)) for p in list(self.parameters()) + list(self.buffers()))
             if self._cache_key == key:
                 return self._cache
             _lib.cache_rebuild_begin(device, self._cache is not None)
@@ -123,13 +134,19 @@ def build(args=None):
                 s = f32(bn.weight) / torch.sqrt(f32(bn.running_var) + bn.eps)
                 return s.contiguous(), (f32(bn.bias) - f32(bn.running_mean) * s).contiguous()
 
-            def cb(conv, bn):
+            split2d = self.conv2d_precision == "f16x3"
+
+            def cb(conv, bn, stem=False):
                 # the kernel axes swapped: this net keeps time innermost, the reference frequency (module docstring)
                 sc, sh = bn_affine(bn)
-                return {"w": ops.pack_conv2d_weight(f32(conv.weight), transpose=True), "k": conv.kernel_size[0], "s": conv.stride[0], "scale": sc, "shift": sh}
+                e = {"w": ops.pack_conv2d_weight(f32(conv.weight), transpose=True), "k": conv.kernel_size[0], "s": conv.stride[0], "scale": sc, "shift": sh}
+                if split2d and not stem:
+                    # (the exact-f32 packing stays: a batch that leaves the f16 range runs on it)
+                    e["w16"], e["descale"] = ops.pack_conv2d_weight_f16x3(f32(conv.weight), transpose=True)
+                return e
 
             sn = self.sequence_network
-            W = {"stem": cb(sn.conv1, sn.bn1), "blocks": []}
+            W = {"stem": cb(sn.conv1, sn.bn1, stem=True), "blocks": [], "split2d": split2d}
             for i in range(4):
                 for blk in getattr(sn, f"layer{i + 1}"):
                     W["blocks"].append({"c1": cb(blk.conv1, blk.bn1), "c2": cb(blk.conv2, blk.bn2),
@@ -159,32 +176,48 @@ def build(args=None):
             return ops.instnorm_rows(ops.melspec_logmel(x, W["window"], W["fb"], W["coef"]))
 
         @staticmethod
-        def _conv(x, e, relu=False):
+        def _conv(x, e, relu=False, flag=None):
+            """`flag` (the batch's int32 overflow flag) selects the split-f16 form"""
+            if flag is not None:
+                return ops.conv2d_f16x3(x, e["w16"], e["descale"], e["k"], e["s"], ch_scale=e["scale"], ch_shift=e["shift"], relu=relu, overflow=flag)
             return ops.conv2d(x, e["w"], e["k"], e["s"], ch_scale=e["scale"], ch_shift=e["shift"], relu=relu)
 
-        def _block(self, x, blk):
+        def _block(self, x, blk, flag=None):
             """ResNetBasicBlock.forward (sidekit/nn.py:57-68) with SELayer.forward (nn.py:23-32)"""
-            out = self._conv(self._conv(x, blk["c1"], relu=True), blk["c2"])
+            out = self._conv(self._conv(x, blk["c1"], relu=True, flag=flag), blk["c2"], flag=flag)
             B, C = out.shape[:2]
             m = ops.row_mean(out.view(B, C, -1))                                    # [B, C, 1]
             g = ops.linear_rows(ops.linear_rows(m, blk["fc0"], relu=True), blk["fc2"])      # the gate's logits
-            r = x if blk["sc"] is None else self._conv(x, blk["sc"])
+            r = x if blk["sc"] is None else self._conv(x, blk["sc"], flag=flag)
             return ops.se_scale_add_relu(out, g, r)
 
         def resnet(self, feats, taps=None):
             """[B, 80, T] -> [B, 256, 10, T']; `taps` (a dict) receives the stem's output and each layer's, for the tests"""
             W = self._prepare(feats.device)
-            x = self._conv(feats.unsqueeze(1), W["stem"], relu=True)
+            stem = self._conv(feats.unsqueeze(1), W["stem"], relu=True)
             if taps is not None:
-                taps["bn1"] = x
-            i = 0
-            for li, n in enumerate(BLOCKS):
-                for _ in range(n):
-                    x = self._block(x, W["blocks"][i])
-                    i += 1
-                if taps is not None:
-                    taps[f"layer{li + 1}"] = x
-            return x
+                taps["bn1"] = stem
+
+            def blocks(flag):
+                x, i = stem, 0
+                for li, n in enumerate(BLOCKS):
+                    for _ in range(n):
+                        x = self._block(x, W["blocks"][i], flag)
+                        i += 1
+                    if taps is not None:
+                        taps[f"layer{li + 1}"] = x
+                return x
+
+            if W["split2d"]:
+                # one zeroed flag per batch (its own allocation: batches on other streams have theirs), read once after the last block
+                flag = torch.zeros(1, dtype=torch.int32, device=feats.device)
+                x = blocks(flag)
+                if int(flag.item()) == 0:
+                    self.last_conv2d_arithmetic = "f16x3"
+                    return x
+                self.split_fallbacks += 1                                         # an activation left the f16 range: exact f32 for this batch
+            self.last_conv2d_arithmetic = "f32"
+            return blocks(None)
 
         def pool(self, x, taps=None):
             """AttentivePooling(256, 10, global_context=True).forward (sidekit/pooling.py:118-138): [B, 2560, T'] -> [B, 5120, 1].

@@ -4,14 +4,17 @@ modules on the same device with the same weights, `channels_last` as the referen
 a batch of 32 utterances of 5 s and for one utterance of 5 s.  Both sides start from the same front-end features (the front end is the
 ECAPA net's and is timed with the HIP side only as part of `hip_with_front_end`).
 
-Both sides run interleaved in every window; a window is `--iters` forwards between two device synchronisations; the median of
+A third side is the same HIP net with `conv2d_precision = "f16x3"` (the blocks' 2-D convs in split-f16 arithmetic, csrc/conv2d16/): the
+comparison that matters for it is `hip_f16x3` against `hip` (exact f32) in the same windows.
+
+All sides run interleaved in every window; a window is `--iters` forwards between two device synchronisations; the median of
 `--windows` windows and their spread (min .. max) are reported, after `--warmup` untimed forwards of each side.
 
 The driver starts every step as a child process of its own under a time limit and stops at the first that fails:
     batch32, single          the two timings, one JSON line each
-    kernels                  the per-kernel split of one batch-32 forward: `rocprofv3 --kernel-trace --stats` around the `once` step,
-                             the ten kernels with the largest total time as one JSON line
-    python tools/bench_xvector_resnet.py [--out profiles/xvector_resnet_bench.jsonl]
+    kernels                  the per-kernel split of three batch-32 forwards with the f16x3 convs: `rocprofv3 --kernel-trace --stats` around
+                             the `once` step, the ten kernels with the largest total time as one JSON line
+    python tools/bench_xvector_resnet.py [--out profiles/xvector_resnet_f16x3_bench.jsonl]
 
 Arithmetic floor: 36 + 1 convs are 22.9 GFLOP per 5 s utterance, 0.73 TFLOP per batch of 32: 4.7 ms at the 155 TFLOP/s the f32 MFMA
 measures on this device."""
@@ -102,9 +105,14 @@ def setup(B):
     net = xvector_resnet.build()(num_speakers=10)
     net.load_state_dict(sd, strict=True)
     net = net.to(DEV)
+    net.conv2d_precision = "f32"
+    net16 = xvector_resnet.build()(num_speakers=10)
+    net16.load_state_dict(sd, strict=True)
+    net16 = net16.to(DEV)
+    net16.conv2d_precision = "f16x3"
     wav = synthetic.rand_batch(1, B, 80000).to(DEV) - 0.5
     feats = net.features(wav)
-    return net, torch_twin(sd), wav, feats
+    return net, net16, torch_twin(sd), wav, feats
 
 
 def window(fn, iters):
@@ -119,10 +127,11 @@ def window(fn, iters):
 
 def step_time(name, B, a):
     import torch
-    net, twin, wav, feats = setup(B)
+    net, net16, twin, wav, feats = setup(B)
     with torch.no_grad():
-        sides = {"hip": lambda: net.embed(feats), "torch_channels_last": lambda: twin(feats), "hip_with_front_end": lambda: net(wav)[1]}
-        x0, x1 = sides["hip"](), sides["torch_channels_last"]()
+        sides = {"hip": lambda: net.embed(feats), "hip_f16x3": lambda: net16.embed(feats), "torch_channels_last": lambda: twin(feats),
+                 "hip_with_front_end": lambda: net(wav)[1]}
+        x0, x1, x2 = sides["hip"](), sides["torch_channels_last"](), sides["hip_f16x3"]()
         for fn in sides.values():
             for _ in range(a.warmup):
                 fn()
@@ -131,10 +140,14 @@ def step_time(name, B, a):
             for k, fn in sides.items():
                 times[k].append(window(fn, a.iters))
     rec = {"measurement": f"xvector_resnet_forward_{name}", "shape": {"B": B, "samples": 80000, "frames": int(feats.shape[2])},
-           "windows": a.windows, "iters_per_window": a.iters, "max_abs_diff_xvector": float((x0 - x1).abs().max())}
+           "windows": a.windows, "iters_per_window": a.iters, "max_abs_diff_xvector": float((x0 - x1).abs().max()),
+           "max_abs_diff_xvector_f16x3_vs_f32": float((x2 - x0).abs().max()), "f16x3_arithmetic_ran": net16.last_conv2d_arithmetic,
+           "f16x3_split_fallbacks": int(net16.split_fallbacks)}
     for k, v in times.items():
         rec[k] = {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
     rec["ratio_torch_over_hip"] = round(rec["torch_channels_last"]["median_ms"] / rec["hip"]["median_ms"], 3)
+    rec["ratio_f32_over_f16x3"] = round(rec["hip"]["median_ms"] / rec["hip_f16x3"]["median_ms"], 3)
+    rec["f16x3_mfma_floor_ms"] = round(3 * 22.9e9 * B / 2.5e15 * 1e3, 3)          # three products per term at the f16 peak
     rec["conv_gflop"] = round(22.9 * B, 1)
     rec["f32_mfma_floor_ms"] = round(22.9e9 * B / 155e12 * 1e3, 3)
     print(json.dumps(rec), flush=True)
@@ -142,10 +155,10 @@ def step_time(name, B, a):
 
 def step_once(a):
     import torch
-    net, _, _, feats = setup(32)
+    _, net16, _, _, feats = setup(32)
     with torch.no_grad():
         for _ in range(3):
-            net.embed(feats)
+            net16.embed(feats)
         torch.cuda.synchronize()
 
 
@@ -161,7 +174,7 @@ def step_kernels(a):
         rows = list(csv.DictReader(open(files[0])))
         total = sum(float(r["TotalDurationNs"]) for r in rows)
         top = sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:10]
-        rec = {"measurement": "xvector_resnet_kernel_split_batch32", "forwards_traced": 3, "setup_included": True,
+        rec = {"measurement": "xvector_resnet_f16x3_kernel_split_batch32", "forwards_traced": 3, "setup_included": True,
                "kernels": [{"name": r["Name"][:70], "calls": int(r["Calls"]), "total_ms": round(float(r["TotalDurationNs"]) / 1e6, 3),
                             "share": round(float(r["TotalDurationNs"]) / total, 4)} for r in top]}
         print(json.dumps(rec), flush=True)
