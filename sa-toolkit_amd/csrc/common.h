@@ -225,4 +225,22 @@ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// polyphase view of ConvTranspose1d(k, stride u, padding pad): output t = q*u + r reads input
+// positions s = q + delta with tap j = r + pad - u*delta, 0 <= j < k.  Returns the tap window
+// [dmin, dmax] over all phases.
+inline void phase_window(int k, int u, int pad, int* dmin, int* dmax) {
+  int lo = 1 << 30, hi = -(1 << 30);
+  for (int r = 0; r < u; ++r) {
+    for (int d = -k; d <= k; ++d) {
+      const int j = r + pad - u * d;
+      if (j >= 0 && j < k) {
+        if (d < lo) lo = d;
+        if (d > hi) hi = d;
+      }
+    }
+  }
+  *dmin = lo;
+  *dmax = hi;
+}
+
 }  // namespace sat

@@ -1644,24 +1644,16 @@ extern "C" int sat_conv1d_packed_dims(int C_in, int C_out, int up, int groups, i
 
 extern "C" int sat_upsample_grouped_supported(int C_in, int C_out, int ksize, int stride, int padding) {
   if (stride != 4 || C_in <= 0 || C_out <= 0 || ksize < stride || padding < 0) return 0;
-  int lo = 1 << 30, hi = -(1 << 30);
-  for (int r = 0; r < stride; ++r)
-    for (int dl = -ksize; dl <= ksize; ++dl) {
-      const int j = r + padding - stride * dl;
-      if (j >= 0 && j < ksize) lo = std::min(lo, dl), hi = std::max(hi, dl);
-    }
+  int lo, hi;
+  phase_window(ksize, stride, padding, &lo, &hi);
   const int slots = hi - lo + 1;
   return C_in % 64 == 0 && C_out % 16 == 0 && C_out * 4 > 128 && slots == 3;
 }
 
 extern "C" uint32_t sat_convtranspose_zero_taps(int ksize, int stride, int padding) {
   if (stride < 1 || stride > 4 || ksize < 1 || padding < 0) return 0;
-  int lo = 1 << 30, hi = -(1 << 30);
-  for (int r = 0; r < stride; ++r)
-    for (int dl = -ksize; dl <= ksize; ++dl) {
-      const int j = r + padding - stride * dl;
-      if (j >= 0 && j < ksize) lo = std::min(lo, dl), hi = std::max(hi, dl);
-    }
+  int lo, hi;
+  phase_window(ksize, stride, padding, &lo, &hi);
   if (hi - lo + 1 > 8) return 0;
   uint32_t mask = 0;
   for (int slot = 0; slot <= hi - lo; ++slot)

@@ -13,24 +13,6 @@ namespace sat {
 
 bool convring_wanted(int rows_g, int T_q, int B);      // conv_ring16.hip: would a k-tap conv of this shape run on the LDS-DMA ring?
 
-// polyphase view of ConvTranspose1d(k, stride u, padding pad): output t = q*u + r reads input
-// positions s = q + delta with tap j = r + pad - u*delta, 0 <= j < k.  Returns the tap window
-// [dmin, dmax] over all phases.
-static void phase_window(int k, int u, int pad, int* dmin, int* dmax) {
-  int lo = 1 << 30, hi = -(1 << 30);
-  for (int r = 0; r < u; ++r) {
-    for (int d = -k; d <= k; ++d) {
-      const int j = r + pad - u * d;
-      if (j >= 0 && j < k) {
-        if (d < lo) lo = d;
-        if (d > hi) hi = d;
-      }
-    }
-  }
-  *dmin = lo;
-  *dmax = hi;
-}
-
 // ---- output stage: leaky_relu(0.01) -> ReflectionPad1d((1,0)) -> Conv1d(C,1,7,pad=3) -> tanh ----
 // HBM-streaming kernel: each block produces 1024 output samples of one utterance from a
 // [C][1024+6] LDS tile.  Padded signal p[i] (i in [0,T]) = lrelu(x[i-1]) for i>=1, p[0] = lrelu(x[1]).
@@ -361,21 +343,18 @@ static int hifigan_get_side(sat_hifigan* h, void* stream, hifigan_side** out) {
   return SAT_OK;
 }
 
+// the integer options of a handle, by name (sat_hifigan_set_option / sat_hifigan_get_option)
+static const struct { const char* name; int sat_hifigan::* field; } HIFIGAN_OPTIONS[] = {
+    {"fuse_pairs", &sat_hifigan::fuse_pairs}, {"fuse_pair64", &sat_hifigan::fuse_pair64}, {"fuse_mrf", &sat_hifigan::fuse_mrf},
+    {"multi_branch", &sat_hifigan::multi_branch}, {"f8_stages", &sat_hifigan::f8_stages}, {"mrf_exact", &sat_hifigan::mrf_exact},
+    {"ups2", &sat_hifigan::ups2}, {"ups_ring", &sat_hifigan::ups_ring}, {"split_acts", &sat_hifigan::split_acts},
+    {"planes_residual", &sat_hifigan::planes_residual}, {"branch_streams", &sat_hifigan::branch_streams}, {"force_f8", &sat_hifigan::force_f8},
+    {"skip_dead_sum", &sat_hifigan::skip_dead_sum}};
+
 extern "C" int sat_hifigan_set_option(sat_hifigan* h, const char* name, int value) {
   SAT_REQUIRE(h && name, "hifigan_set_option: null pointer");
-  if (std::string(name) == "fuse_pairs") { h->fuse_pairs = value; return SAT_OK; }
-  if (std::string(name) == "fuse_pair64") { h->fuse_pair64 = value; return SAT_OK; }
-  if (std::string(name) == "fuse_mrf") { h->fuse_mrf = value; return SAT_OK; }
-  if (std::string(name) == "multi_branch") { h->multi_branch = value; return SAT_OK; }
-  if (std::string(name) == "f8_stages") { h->f8_stages = value; return SAT_OK; }
-  if (std::string(name) == "mrf_exact") { h->mrf_exact = value; return SAT_OK; }
-  if (std::string(name) == "ups2") { h->ups2 = value; return SAT_OK; }
-  if (std::string(name) == "ups_ring") { h->ups_ring = value; return SAT_OK; }
-  if (std::string(name) == "split_acts") { h->split_acts = value; return SAT_OK; }
-  if (std::string(name) == "planes_residual") { h->planes_residual = value; return SAT_OK; }
-  if (std::string(name) == "branch_streams") { h->branch_streams = value; return SAT_OK; }
-  if (std::string(name) == "force_f8") { h->force_f8 = value; return SAT_OK; }
-  if (std::string(name) == "skip_dead_sum") { h->skip_dead_sum = value; return SAT_OK; }
+  for (const auto& o : HIFIGAN_OPTIONS)
+    if (std::string(name) == o.name) { h->*o.field = value; return SAT_OK; }
   set_error("hifigan_set_option: unknown option %s", name);
   return SAT_ERR_INVALID;
 }
@@ -384,19 +363,8 @@ extern "C" int sat_hifigan_get_option(const sat_hifigan* h, const char* name, in
   SAT_REQUIRE(h && name && value, "hifigan_get_option: null pointer");
   const std::string n(name);
   if (n == "last_f8_stages") { *value = h->last_f8_stages.load(std::memory_order_relaxed); return SAT_OK; }
-  if (n == "fuse_pairs") { *value = h->fuse_pairs; return SAT_OK; }
-  if (n == "fuse_pair64") { *value = h->fuse_pair64; return SAT_OK; }
-  if (n == "fuse_mrf") { *value = h->fuse_mrf; return SAT_OK; }
-  if (n == "multi_branch") { *value = h->multi_branch; return SAT_OK; }
-  if (n == "f8_stages") { *value = h->f8_stages; return SAT_OK; }
-  if (n == "mrf_exact") { *value = h->mrf_exact; return SAT_OK; }
-  if (n == "ups2") { *value = h->ups2; return SAT_OK; }
-  if (n == "ups_ring") { *value = h->ups_ring; return SAT_OK; }
-  if (n == "split_acts") { *value = h->split_acts; return SAT_OK; }
-  if (n == "planes_residual") { *value = h->planes_residual; return SAT_OK; }
-  if (n == "branch_streams") { *value = h->branch_streams; return SAT_OK; }
-  if (n == "force_f8") { *value = h->force_f8; return SAT_OK; }
-  if (n == "skip_dead_sum") { *value = h->skip_dead_sum; return SAT_OK; }
+  for (const auto& o : HIFIGAN_OPTIONS)
+    if (n == o.name) { *value = h->*o.field; return SAT_OK; }
   set_error("hifigan_get_option: unknown option %s", name);
   return SAT_ERR_INVALID;
 }
@@ -429,6 +397,541 @@ extern "C" int sat_hifigan_convpost_f32(const float* x, const float* w, const fl
   return SAT_OK;
 }
 
+// ---- the forward: descriptors of the ResBlock convs, then one function per phase of a stage ----
+
+static sat_conv1d_desc base_desc(int B, int Cin, int Cout, int Tin, int Tq, int up) {
+  sat_conv1d_desc d{};
+  d.B = B;
+  d.C_in = Cin;
+  d.T_in = Tin;
+  d.C_out = Cout;
+  d.T_q = Tq;
+  d.ksize = 1;
+  d.dilation = 1;
+  d.stride = 1;
+  d.groups = 1;
+  d.up = up;
+  d.x_cstride = Tin;
+  d.x_bstride = (int64_t)Cin * Tin;
+  d.y_cstride = (int64_t)Tq * up;
+  d.y_bstride = (int64_t)Cout * Tq * up;
+  d.res_tstride = 1;
+  return d;
+}
+
+// where an activation lives: as f32, as split planes, as the 8-bit sidecar of the planes (null: not in that form)
+struct act_loc {
+  float* f = nullptr;
+  void* s = nullptr;
+  void* s8 = nullptr;
+};
+
+// buffers of one ResBlock branch: the inner activation of a step, the outputs of steps 0 and 1, the MRF sum, the next stage's input planes
+struct rb_bufs {
+  act_loc t, out[2];
+  float* acc = nullptr;
+  void* next = nullptr;
+};
+
+// where the output of step `pair` of branch j goes and how it is stored
+struct step_out {
+  act_loc dst;
+  int no_y = 0, accum = 0;
+  float accum_div = 0.f;
+  int accum_no_store = 0;
+};
+
+// Steps 0 and 1 ping-pong between the branch's two outputs; step 2 goes into the MRF sum (xs += resblock(x), divided by num_kernels with
+// the last branch: archi.py:82-86), the last branch also writing the planes the next stage reads.  The f32 mean of a stage that is not the
+// last is read by nobody (the next upsampler takes its planes): the last branch's launch does not store it (sat_conv1d_desc.accum_no_store)
+static step_out step_output(int pair, int j, int nk, bool last_stage, bool skip_dead_sum, bool planes_res, const rb_bufs& b) {
+  step_out o;
+  if (pair < 2) {
+    o.dst = b.out[pair];
+    o.no_y = planes_res;
+    return o;
+  }
+  o.dst.f = b.acc;
+  o.dst.s = (j == nk - 1 && !last_stage) ? b.next : nullptr;
+  o.accum = j > 0;
+  o.accum_div = (j == nk - 1) ? (float)nk : 0.f;
+  o.accum_no_store = skip_dead_sum && planes_res && j > 0 && o.dst.s != nullptr;
+  return o;
+}
+
+// first conv of a ResBlock1 step, xt = c1(leaky_relu(x, 0.1)) (nn.py:183-184): the dilated one.  x as planes: the inner activation leaves as
+// planes only; `f8r`: SAT_CONV_F16F8R on the conv's second packing.  *w = the packing to launch with
+static sat_conv1d_desc rb_conv1_desc(int B, int Cn, int Tn, int rk, int dil, const sat_hifigan::Conv& cv, int mode, bool f8r, const act_loc& x,
+                                     const act_loc& t, const void** w) {
+  sat_conv1d_desc d = base_desc(B, Cn, Cn, Tn, Tn, 1);
+  d.ksize = rk;
+  d.dilation = dil;
+  d.pad_left = (rk * dil - dil) / 2;
+  d.bias = cv.bias;
+  d.w_descale = cv.descale;
+  d.mode = mode;
+  if (x.s) {
+    d.x_split = x.s;
+    d.y_split = t.s;
+    d.y_split_slope = 0.1f;
+    d.no_y = 1;
+  } else {
+    d.in_lrelu = 1;
+    d.in_slope = 0.1f;
+  }
+  *w = cv.w;
+  if (f8r) {
+    d.mode = SAT_CONV_F16F8R;
+    d.x_split8 = x.s8;
+    d.y_split8 = t.s8;
+    d.y_split_hi_only = 1;          // the inner activation is only ever a matrix operand
+    *w = cv.w8;
+  }
+  return d;
+}
+
+// second conv of the step, x = c2(leaky_relu(xt, 0.1)) + x (nn.py:185-186).  The residual is the step's input: from its split planes
+// (hi + lo, leaky-relu undone) when the format carries both halves, so no f32 copy of the activations is written inside a resblock
+static sat_conv1d_desc rb_conv2_desc(int B, int Cn, int Tn, int rk, const sat_hifigan::Conv& cv, int mode, bool f8r, const act_loc& t,
+                                     const act_loc& res, bool planes_res, const step_out& o, const void** w) {
+  sat_conv1d_desc d = base_desc(B, Cn, Cn, Tn, Tn, 1);
+  d.ksize = rk;
+  d.dilation = 1;
+  d.pad_left = (rk - 1) / 2;
+  d.in_lrelu = 1;
+  d.in_slope = 0.1f;
+  d.bias = cv.bias;
+  d.w_descale = cv.descale;
+  d.mode = mode;
+  if (planes_res) {
+    d.res_split = res.s;
+    d.res_split_slope = 0.1f;
+  } else {
+    d.res = res.f;
+    d.res_cstride = Tn;
+    d.res_bstride = (int64_t)Cn * Tn;
+  }
+  d.res_scale = 1.f;
+  if (t.s) {
+    d.x_split = t.s;
+    d.y_split_slope = 0.1f;
+  }
+  d.no_y = o.no_y;
+  d.accum = o.accum;
+  d.accum_div = o.accum_div;
+  d.accum_no_store = o.accum_no_store;
+  d.y_split = o.dst.s;
+  *w = cv.w;
+  if (f8r) {
+    d.mode = SAT_CONV_F16F8R;
+    d.x_split8 = t.s8;
+    d.y_split8 = o.dst.s8;
+    *w = cv.w8;
+  }
+  return d;
+}
+
+// the fused step (sat_resblock_pair_scaled_f16x3) takes the second conv's descriptor with the first conv's dilation and input
+static sat_conv1d_desc rb_pair_desc(sat_conv1d_desc d2, int dil, const void* x_split) {
+  d2.dilation = dil;
+  d2.x_split = x_split;
+  return d2;
+}
+
+// one forward's constants and workspace slots (WS_SLOTS: slot 0 the upsampled x in f32, 1 its planes, 2 the MRF sum, 3 / 4 the stage
+// input planes, then per branch the planes of the inner activation and of the two step outputs, each output with an f32 twin)
+struct fwd_ctx {
+  const sat_hifigan* h;
+  int B;
+  void* stream;
+  char* ws;
+  size_t slot;
+  // split-plane pipeline only
+  int cmode = 0;                  // mode of every conv behind conv_pre: SAT_CONV_F16X3 or SAT_CONV_F16F8
+  bool planes_res = false;        // residuals rebuilt from the planes: no f32 twin is written
+  hifigan_side* side = nullptr;
+  void* XS = nullptr;             // stage input planes
+  void* XSn = nullptr;            // the next stage's
+
+  char* at(int i) const { return ws + (size_t)i * slot; }
+  // the 8-bit (e5m2) sidecars (half a slot each: 2 bytes per element) lie in the slots of the f32 twins, which planes_res leaves unwritten
+  act_loc H() const { return {(float*)at(0), at(1), at(0)}; }
+  float* ACCf() const { return (float*)at(2); }
+  rb_bufs branch(int j) const {
+    const int b = 5 + j * 5;
+    rb_bufs r;
+    r.t = {nullptr, at(b), at(b + 1)};
+    r.out[0] = {(float*)at(b + 1), at(b + 2), at(b + 1) + slot / 2};
+    r.out[1] = {(float*)at(b + 3), at(b + 4), at(b + 3)};
+    r.acc = ACCf();
+    r.next = XSn;
+    return r;
+  }
+};
+
+struct stage_dims {
+  int i, C, Tc, Cn, Tn;       // stage index; channels and frames before and behind the upsampler
+  bool last;
+};
+
+// step `pair` of branch j on the split-plane pipeline: both descriptors, their weights, where the step reads and writes
+struct rb_step {
+  sat_conv1d_desc d1, d2;
+  const void *w1, *w2;
+  act_loc in;
+  step_out out;
+};
+
+static rb_step planes_step(const fwd_ctx& c, const stage_dims& st, int j, int pair, bool f8r) {
+  const sat_hifigan* h = c.h;
+  const int rk = h->rb_kernels[j];
+  const rb_bufs b = c.branch(j);
+  rb_step s;
+  s.in = pair == 0 ? c.H() : b.out[pair - 1];
+  s.out = step_output(pair, j, h->n_rbk(), st.last, h->skip_dead_sum, c.planes_res, b);
+  s.d1 = rb_conv1_desc(c.B, st.Cn, st.Tn, rk, h->rb_dil[j * 3 + pair], h->convs[h->id_rb(st.i, j, pair, 0)], c.cmode, f8r, s.in, b.t, &s.w1);
+  s.d2 = rb_conv2_desc(c.B, st.Cn, st.Tn, rk, h->convs[h->id_rb(st.i, j, pair, 1)], c.cmode, f8r, b.t, s.in, c.planes_res, s.out, &s.w2);
+  return s;
+}
+
+// thick stages (C > 64): the i-th conv of all MRF branches as one sat_conv1d_multi_f32 call
+static bool stage_is_thick(const fwd_ctx& c, const stage_dims& st) {
+  const int nk = c.h->n_rbk();
+  const bool fan = c.side && st.i < c.h->branch_streams;
+  return c.h->multi_branch && c.planes_res && !fan && nk >= 2 && nk <= 3 && st.Cn > 64;
+}
+
+// this stage's ResBlock convs with 8-bit cross terms (SAT_CONV_F16F8R): the one-launch-per-conv path of the thick stages, every
+// conv's second packing installed, and a batch the ring kernel would serve anyway (small batches keep the f16x3 tiles)
+static bool stage_uses_f8r(const fwd_ctx& c, const stage_dims& st) {
+  const sat_hifigan* h = c.h;
+  const int nk = h->n_rbk();
+  bool use_f8 = ((h->f8_stages >> st.i) & 1) && stage_is_thick(c, st) && st.Cn % 32 == 0 && (h->force_f8 || convring_wanted(st.Cn, st.Tn, c.B));
+  for (int j = 0; j < nk && use_f8; ++j)
+    for (int pair = 0; pair < 3; ++pair)
+      use_f8 = use_f8 && h->convs[h->id_rb(st.i, j, pair, 0)].w8 && h->convs[h->id_rb(st.i, j, pair, 1)].w8 &&
+               (h->rb_kernels[j] - 1) * h->rb_dil[j * 3 + pair] <= 64 && h->rb_kernels[j] >= 3;
+  // ... and every descriptor of the stage — the ones stage_thick launches — asked of the ring kernel itself (convring_supports has more
+  // conditions than convring_wanted — 31-bit output slabs for the fast epilogue, an even step count, ...): a stage one of whose convs it
+  // would refuse keeps the f16x3 packing, whose dispatch has the register-staged tiles to fall back on
+  for (int j = 0; j < nk && use_f8; ++j)
+    for (int pair = 0; pair < 3 && use_f8; ++pair) {
+      const rb_step s = planes_step(c, st, j, pair, true);
+      use_f8 = sat_conv1d_f8r_supported(&s.d1) != 0 && sat_conv1d_f8r_supported(&s.d2) != 0;
+    }
+  return use_f8;
+}
+
+// x = ups[i](x) from the stage input planes (which carry the leaky-relu) to the planes of H
+static int stage_upsample(const fwd_ctx& c, const stage_dims& st, bool use_f8) {
+  const sat_hifigan* h = c.h;
+  const int u = h->up_rates[st.i], k = h->up_kernels[st.i];
+  const auto& cv = h->convs[h->id_up(st.i)];
+  const act_loc H = c.H();
+  const bool planes = c.cmode == SAT_CONV_F16X3 && h->planes_residual;
+  int lo, hi;
+  phase_window(k, u, (k - u) / 2, &lo, &hi);
+  sat_conv1d_desc d = base_desc(c.B, st.C, st.Cn, st.Tc, st.Tc, u);
+  d.ksize = hi - lo + 1;
+  d.pad_left = -lo;
+  d.bias = cv.bias;
+  d.w_descale = cv.descale;
+  d.mode = c.cmode;
+  d.x_split = c.XS;
+  // rates 2 and 4: the transposed conv writes the split planes itself (LDS-transposed epilogue); other
+  // rates (5: a block's 64 rows are not whole channel groups) store f32 and split in a streaming pass
+  const int co_b = st.Cn * u > 32 ? 64 : 32;
+  const bool direct = planes && co_b % (8 * u) == 0;
+  int s;
+  if (h->ups2 && planes && sat_upsample2_supported(st.C, k, u, (k - u) / 2)) {
+    s = sat_upsample2_f16x3(c.XS, cv.w, cv.bias, cv.descale, H.s, 0.1f, c.B, st.C, st.Tc, c.stream);
+    if (s != SAT_OK) return s;
+  } else if (h->ups_ring && sat_upsample_grouped_supported(st.C, st.Cn, k, u, (k - u) / 2)) {
+    // rows grouped by phase (the packer consulted the same rule): the LDS-DMA ring, zero tap slots skipped (conv_ring16.hip)
+    if (!planes) {
+      set_error("hifigan: option ups_ring (packed rows of the stride-4 upsamplers grouped by phase) needs split-f16 weights and the split-plane pipeline");
+      return SAT_ERR_INVALID;
+    }
+    d.y_split = H.s;
+    d.y_split_slope = 0.1f;
+    d.no_y = 1;
+    d.up_grouped = 1;
+    d.up_zero_taps = sat_convtranspose_zero_taps(k, u, (k - u) / 2);
+    if (use_f8) d.y_split8 = H.s8;        // the ring's upsampler epilogue writes the sidecar next to the planes
+    s = sat_conv1d_f32(&d, nullptr, cv.w, nullptr, c.stream);
+    if (s != SAT_OK) return s;
+  } else if (direct) {
+    d.y_split = H.s;
+    d.y_split_slope = 0.1f;
+    d.no_y = 1;
+    s = sat_conv1d_f32(&d, nullptr, cv.w, nullptr, c.stream);
+    if (s != SAT_OK) return s;
+  } else {
+    s = sat_conv1d_f32(&d, nullptr, cv.w, H.f, c.stream);
+    if (s != SAT_OK) return s;
+    s = sat_act_split_f32(H.f, H.s, c.B, st.Cn, st.Tn, 0.1f, c.cmode == SAT_CONV_F16F8 ? SAT_SPLIT_F8 : SAT_SPLIT_F16, c.stream);
+    if (s != SAT_OK) return s;
+  }
+  if (use_f8 && !d.y_split8) {
+    s = sat_planes_f8_sidecar(H.s, H.s8, c.B, st.Cn, st.Tn, c.stream);      // (the f32 form of H is dead behind the split pass)
+    if (s != SAT_OK) return s;
+  }
+  if (h->range_probe) {
+    s = planes_range_probe(H.s, c.B, st.Cn, st.Tn, h->range_probe + 2 * st.i, c.stream);
+    if (s != SAT_OK) return s;
+  }
+  return SAT_OK;
+}
+
+static bool stage_mrf_fusable(const fwd_ctx& c, const stage_dims& st) {
+  const sat_hifigan* h = c.h;
+  return h->fuse_mrf && c.planes_res && h->fuse_pairs && h->n_rbk() <= 3 &&
+         sat_resblock_mrf_supported(st.Cn, h->n_rbk(), h->rb_kernels.data(), h->rb_dil.data()) &&
+         sat_resblock_mrf_scratch_bytes(h->n_rbk(), h->rb_kernels.data()) <= WS_MRF_SCRATCH;
+}
+
+// the whole MRF block of this stage in one launch (mrf.hip): same bits as stage_branches
+static int stage_mrf_fused(const fwd_ctx& c, const stage_dims& st) {
+  const sat_hifigan* h = c.h;
+  const int nk = h->n_rbk();
+  sat_mrf_desc m{};
+  m.B = c.B; m.C = st.Cn; m.T = st.Tn; m.n_branches = nk;
+  for (int j = 0; j < nk; ++j) {
+    m.ksize[j] = h->rb_kernels[j];
+    for (int pair = 0; pair < 3; ++pair) {
+      m.dilation[j][pair] = h->rb_dil[j * 3 + pair];
+      for (int which = 0; which < 2; ++which) {
+        const auto& cv = h->convs[h->id_rb(st.i, j, pair, which)];
+        m.w[j][pair][which] = cv.w;
+        m.bias[j][pair][which] = cv.bias;
+        m.w_descale[j][pair][which] = cv.descale;
+      }
+    }
+  }
+  m.slope = 0.1f;
+  m.x_split = c.H().s;
+  m.y = c.ACCf();
+  m.y_split = st.last ? nullptr : c.XSn;
+  m.y_split_slope = 0.1f;
+  m.out_div = (float)nk;
+  m.residual_from_planes = !h->mrf_exact;
+  m.scratch = c.at(WS_SLOTS);
+  m.scratch_bytes = WS_MRF_SCRATCH;
+  return sat_resblock_mrf_f16x3(&m, c.stream);
+}
+
+// The thick stages (no fused ResBlock step: C > 64): the i-th conv of ALL branches in one launch
+// (sat_conv1d_multi_f32: the LDS-DMA ring kernel walks the tiles of the three kernel sizes; the MRF sum is
+// accumulated branch by branch inside a block, in the order of stage_branches) — 6 launches per stage instead of 18.
+static int stage_thick(const fwd_ctx& c, const stage_dims& st, bool use_f8) {
+  const sat_hifigan* h = c.h;
+  const int nk = h->n_rbk();
+  const float* xnull[3] = {nullptr, nullptr, nullptr};
+  for (int pair = 0; pair < 3; ++pair) {
+    sat_conv1d_desc d1[3], d2[3];
+    const void* w1[3];
+    const void* w2[3];
+    float* y1[3] = {nullptr, nullptr, nullptr};
+    float* y2[3];
+    void* dst_s[3];
+    for (int j = 0; j < nk; ++j) {
+      const rb_step s = planes_step(c, st, j, pair, use_f8);
+      d1[j] = s.d1, w1[j] = s.w1;
+      d2[j] = s.d2, w2[j] = s.w2;
+      y2[j] = s.out.no_y ? nullptr : s.out.dst.f;
+      dst_s[j] = s.out.dst.s;
+    }
+    int s = sat_conv1d_multi_f32(d1, xnull, w1, y1, nk, c.stream);
+    if (s != SAT_OK) return s;
+    s = sat_conv1d_multi_f32(d2, xnull, w2, y2, nk, c.stream);
+    if (s != SAT_OK) return s;
+    for (int j = 0; j < nk && h->range_probe; ++j) {
+      s = planes_range_probe(c.branch(j).t.s, c.B, st.Cn, st.Tn, h->range_probe + 2 * st.i, c.stream);
+      if (s == SAT_OK && dst_s[j]) s = planes_range_probe(dst_s[j], c.B, st.Cn, st.Tn, h->range_probe + 2 * st.i, c.stream);
+      if (s != SAT_OK) return s;
+    }
+  }
+  return SAT_OK;
+}
+
+// branch by branch: a step as the fused pair launch where one serves it, else as two launches; with option branch_streams branch j
+// on its own stream (the last, longest branch on the caller's), the order of the sum kept by events
+static int stage_branches(const fwd_ctx& c, const stage_dims& st) {
+  const sat_hifigan* h = c.h;
+  const int nk = h->n_rbk(), Cn = st.Cn;
+  hifigan_side* side = c.side;
+  const bool fan = side && st.i < h->branch_streams;   // option value = number of leading stages fanned out
+  if (fan) {
+    SAT_HIP(hipEventRecord(side->fork, (hipStream_t)c.stream));
+    for (auto sd : side->s) SAT_HIP(hipStreamWaitEvent(sd, side->fork, 0));
+  }
+  for (int j = 0; j < nk; ++j) {
+    const int rk = h->rb_kernels[j];
+    void* stream_j = fan && j < 2 ? (void*)side->s[j] : c.stream;
+    for (int pair = 0; pair < 3; ++pair) {
+      const rb_step p = planes_step(c, st, j, pair, false);
+      const auto& cv1 = h->convs[h->id_rb(st.i, j, pair, 0)];
+      const bool fused = (Cn <= 32 || (Cn == 64 && c.planes_res && (h->fuse_pair64 & (rk == 3 ? 1 : rk == 7 ? 2 : 4)))) && h->fuse_pairs &&
+                         c.cmode == SAT_CONV_F16X3;
+      int s;
+      if (!fused) {
+        s = sat_conv1d_f32(&p.d1, nullptr, p.w1, nullptr, stream_j);
+        if (s != SAT_OK) return s;
+      }
+      // the MRF sum is read-modify-write on ACC: branch j's last kernel waits for branch j-1's
+      if (fan && pair == 2 && j > 0) SAT_HIP(hipStreamWaitEvent((hipStream_t)stream_j, side->acc[j - 1], 0));
+      if (fused) {
+        const sat_conv1d_desc df = rb_pair_desc(p.d2, h->rb_dil[j * 3 + pair], p.in.s);
+        s = sat_resblock_pair_scaled_f16x3(&df, c.planes_res ? nullptr : p.in.f, cv1.w, cv1.bias, cv1.descale, p.w2, p.out.dst.f, stream_j);
+      } else {
+        s = sat_conv1d_f32(&p.d2, nullptr, p.w2, p.out.dst.f, stream_j);
+      }
+      if (s != SAT_OK) return s;
+      if (fan && pair == 2) SAT_HIP(hipEventRecord(side->acc[j], (hipStream_t)stream_j));
+    }
+  }
+  return SAT_OK;
+}
+
+// ---- split-plane pipeline: every producer writes the hi|lo f16 planes of leaky_relu(y, 0.1) the
+// consumer will multiply with, so inputs are staged with 16-byte copies and converted once ----
+static int forward_planes(fwd_ctx& c, const float* x, float* y, int T) {
+  const sat_hifigan* h = c.h;
+  c.cmode = h->convs[1].mode;                                              // SAT_CONV_F16X3 or SAT_CONV_F16F8
+  c.planes_res = c.cmode == SAT_CONV_F16X3 && h->planes_residual;
+  c.XS = c.at(3);
+  c.XSn = c.at(4);
+  if (c.planes_res && h->branch_streams && h->n_rbk() == 3) {
+    int st = hifigan_get_side(const_cast<sat_hifigan*>(h), c.stream, &c.side);
+    if (st != SAT_OK) return st;
+  }
+  {
+    sat_conv1d_desc d = base_desc(c.B, h->in_ch, h->c0, T, T, 1);
+    d.ksize = 7;
+    d.pad_left = 3;
+    d.bias = h->convs[0].bias;
+    d.w_descale = h->convs[0].descale;
+    d.mode = SAT_CONV_F16X3;
+    d.y_split = c.XS;
+    d.y_split_slope = 0.1f;
+    d.y_split_format = c.cmode == SAT_CONV_F16F8 ? 2 : 1;                  // plane format every consumer reads
+    d.no_y = 1;
+    int s = sat_conv1d_f32(&d, x, h->convs[0].w, nullptr, c.stream);
+    if (s != SAT_OK) return s;
+  }
+  int C = h->c0, Tc = T;
+  int f8_mask = 0;
+  for (int i = 0; i < h->n_ups(); ++i) {
+    const stage_dims st = {i, C, Tc, C / 2, Tc * h->up_rates[i], i == h->n_ups() - 1};
+    const bool use_f8 = stage_uses_f8r(c, st);
+    if (use_f8) f8_mask |= 1 << i;
+    int s = stage_upsample(c, st, use_f8);
+    if (s != SAT_OK) return s;
+    if (stage_mrf_fusable(c, st)) s = stage_mrf_fused(c, st);
+    else if (stage_is_thick(c, st)) s = stage_thick(c, st, use_f8);
+    else s = stage_branches(c, st);
+    if (s != SAT_OK) return s;
+    void* t = c.XS;
+    c.XS = c.XSn;
+    c.XSn = t;
+    C = st.Cn;
+    Tc = st.Tn;
+  }
+  h->last_f8_stages.store(f8_mask, std::memory_order_relaxed);
+  return sat_hifigan_convpost_f32(c.ACCf(), (const float*)h->convs[h->id_post()].w, h->convs[h->id_post()].bias, y, c.B, C, Tc, c.stream);
+}
+
+// one stage of the f32-handover pipeline: X -> H (upsampled) -> the MRF mean in b.acc
+static int handover_stage(const fwd_ctx& c, const stage_dims& st, const float* X, float* H, const rb_bufs& b) {
+  const sat_hifigan* h = c.h;
+  const int u = h->up_rates[st.i], k = h->up_kernels[st.i], nk = h->n_rbk(), Cn = st.Cn, Tn = st.Tn;
+  // x = leaky_relu(x, 0.1); x = ups[i](x)   (archi.py:80-81)
+  {
+    int lo, hi;
+    phase_window(k, u, (k - u) / 2, &lo, &hi);
+    if (h->ups_ring && sat_upsample_grouped_supported(st.C, Cn, k, u, (k - u) / 2)) {
+      set_error("hifigan: option ups_ring (packed rows of the stride-4 upsamplers grouped by phase) needs the split-plane pipeline (split_acts)");
+      return SAT_ERR_INVALID;
+    }
+    const auto& cv = h->convs[h->id_up(st.i)];
+    sat_conv1d_desc d = base_desc(c.B, st.C, Cn, st.Tc, st.Tc, u);
+    d.ksize = hi - lo + 1;
+    d.pad_left = -lo;
+    d.in_lrelu = 1;
+    d.in_slope = 0.1f;
+    d.bias = cv.bias;
+    d.w_descale = cv.descale;
+    d.mode = cv.mode;
+    int s = sat_conv1d_f32(&d, X, cv.w, H, c.stream);
+    if (s != SAT_OK) return s;
+  }
+  // xs = sum_j resblock_j(x); x = xs / num_kernels   (archi.py:82-86)
+  for (int j = 0; j < nk; ++j) {
+    const int rk = h->rb_kernels[j];
+    for (int pair = 0; pair < 3; ++pair) {
+      const int dil = h->rb_dil[j * 3 + pair];
+      const auto& cv1 = h->convs[h->id_rb(st.i, j, pair, 0)];
+      const auto& cv2 = h->convs[h->id_rb(st.i, j, pair, 1)];
+      act_loc r;
+      r.f = pair == 0 ? H : b.out[pair - 1].f;
+      const step_out o = step_output(pair, j, nk, st.last, h->skip_dead_sum, false, b);
+      const void *w1, *w2;
+      // x = c2(leaky_relu(xt, 0.1)) + x with xt = c1(leaky_relu(x, 0.1))
+      const sat_conv1d_desc d2 = rb_conv2_desc(c.B, Cn, Tn, rk, cv2, cv2.mode, false, b.t, r, false, o, &w2);
+      int s;
+      if (Cn <= 32 && Cn % 16 == 0 && cv1.mode == SAT_CONV_F16X3 && cv2.mode == SAT_CONV_F16X3 && h->fuse_pairs) {
+        // thin stages sit on the HBM roofline: one fused kernel, the intermediate stays in LDS
+        const sat_conv1d_desc df = rb_pair_desc(d2, dil, nullptr);
+        s = sat_resblock_pair_scaled_f16x3(&df, r.f, cv1.w, cv1.bias, cv1.descale, w2, o.dst.f, c.stream);
+        if (s != SAT_OK) return s;
+      } else {
+        const sat_conv1d_desc d1 = rb_conv1_desc(c.B, Cn, Tn, rk, dil, cv1, cv1.mode, false, r, b.t, &w1);
+        s = sat_conv1d_f32(&d1, r.f, w1, b.t.f, c.stream);
+        if (s != SAT_OK) return s;
+        s = sat_conv1d_f32(&d2, b.t.f, w2, o.dst.f, c.stream);
+        if (s != SAT_OK) return s;
+      }
+    }
+  }
+  return SAT_OK;
+}
+
+// ---- f32-handover pipeline: f32 activations between the layers, split inside every kernel ----
+static int forward_handover(const fwd_ctx& c, const float* x, float* y, int T) {
+  const sat_hifigan* h = c.h;
+  float* X = (float*)c.at(0);     // stage input
+  float* H = (float*)c.at(1);     // upsampled
+  rb_bufs b;                      // (no planes: every act_loc is f32 only)
+  b.t.f = (float*)c.at(2);        // inner activation of a resblock pair
+  b.out[0].f = (float*)c.at(3);
+  b.out[1].f = (float*)c.at(4);
+  b.acc = (float*)c.at(5);        // MRF sum -> next stage input
+  // conv_pre (archi.py:78)
+  {
+    sat_conv1d_desc d = base_desc(c.B, h->in_ch, h->c0, T, T, 1);
+    d.ksize = 7;
+    d.pad_left = 3;
+    d.bias = h->convs[0].bias;
+    d.w_descale = h->convs[0].descale;
+    d.mode = h->convs[0].mode;
+    int s = sat_conv1d_f32(&d, x, h->convs[0].w, X, c.stream);
+    if (s != SAT_OK) return s;
+  }
+  int C = h->c0, Tc = T;
+  for (int i = 0; i < h->n_ups(); ++i) {
+    const stage_dims st = {i, C, Tc, C / 2, Tc * h->up_rates[i], i == h->n_ups() - 1};
+    int s = handover_stage(c, st, X, H, b);
+    if (s != SAT_OK) return s;
+    float* t = X;
+    X = b.acc;
+    b.acc = t;
+    C = st.Cn;
+    Tc = st.Tn;
+  }
+  // x = leaky_relu(x); reflection_pad; conv_post; tanh   (archi.py:87-90)
+  return sat_hifigan_convpost_f32(X, (const float*)h->convs[h->id_post()].w, h->convs[h->id_post()].bias, y, c.B, C, Tc, c.stream);
+}
+
 extern "C" int sat_hifigan_forward_f32(const sat_hifigan* h, const float* x, float* y, void* workspace,
                                        size_t workspace_bytes, int B, int T, void* stream) {
   SAT_REQUIRE(h && x && y && workspace, "hifigan_forward: null pointer");
@@ -436,497 +939,8 @@ extern "C" int sat_hifigan_forward_f32(const sat_hifigan* h, const float* x, flo
   for (size_t i = 0; i < h->convs.size(); ++i)
     SAT_REQUIRE(h->convs[i].w && h->convs[i].bias, "hifigan_forward: conv %zu has no weights", i);
   SAT_REQUIRE_WORKSPACE(workspace_bytes >= sat_hifigan_workspace_bytes(h, B, T), "hifigan_forward: workspace too small");
-  const size_t slot = align_up(hifigan_max_elems(h, B, T) * sizeof(float), 256);
-  float* buf[6];
-  for (int i = 0; i < 6; ++i) buf[i] = (float*)((char*)workspace + i * slot);
-  float* X = buf[0];    // stage input
-  float* H = buf[1];    // upsampled
-  float* T1 = buf[2];   // inner activation of a resblock pair
-  float* RA = buf[3];
-  float* RB = buf[4];
-  float* ACC = buf[5];  // MRF sum -> next stage input
-
-  auto base_desc = [&](int Cin, int Cout, int Tin, int Tq, int up) {
-    sat_conv1d_desc d{};
-    d.B = B;
-    d.C_in = Cin;
-    d.T_in = Tin;
-    d.C_out = Cout;
-    d.T_q = Tq;
-    d.ksize = 1;
-    d.dilation = 1;
-    d.stride = 1;
-    d.groups = 1;
-    d.up = up;
-    d.x_cstride = Tin;
-    d.x_bstride = (int64_t)Cin * Tin;
-    d.y_cstride = (int64_t)Tq * up;
-    d.y_bstride = (int64_t)Cout * Tq * up;
-    d.res_tstride = 1;
-    return d;
-  };
-
-  if (hifigan_split_acts(h)) {
-    // ---- split-plane pipeline: every producer writes the hi|lo f16 planes of leaky_relu(y, 0.1) the
-    // consumer will multiply with, so inputs are staged with 16-byte copies and converted once ----
-    const int cmode = h->convs[1].mode;                                // SAT_CONV_F16X3 or SAT_CONV_F16F8
-    const int yfmt = cmode == SAT_CONV_F16F8 ? 2 : 1;                  // plane format every consumer reads
-    char* ws = (char*)workspace;
-    float* Hf = (float*)(ws + 0 * slot);   void* Hs = ws + 1 * slot;    // upsampled x (f32 for the split pass, planes)
-    float* ACCf = (float*)(ws + 2 * slot);                             // MRF sum
-    void* XS = ws + 3 * slot;                                          // stage input planes
-    void* XSn = ws + 4 * slot;
-    // per resblock branch: planes of the inner activation and of the two ping-pong outputs (+ their f32
-    // twins, only written when residuals are not rebuilt from planes)
-    auto br = [&](int j, int which) { return ws + (size_t)(5 + j * 5 + which) * slot; };
-    const bool planes_res_all = cmode == SAT_CONV_F16X3 && h->planes_residual;
-    hifigan_side* side = nullptr;
-    const int nk0 = h->n_rbk();
-    if (planes_res_all && h->branch_streams && nk0 == 3) {
-      int st = hifigan_get_side(const_cast<sat_hifigan*>(h), stream, &side);
-      if (st != SAT_OK) return st;
-    }
-    {
-      sat_conv1d_desc d = base_desc(h->in_ch, h->c0, T, T, 1);
-      d.ksize = 7;
-      d.pad_left = 3;
-      d.bias = h->convs[0].bias;
-      d.w_descale = h->convs[0].descale;
-      d.mode = SAT_CONV_F16X3;
-      d.y_split = XS;
-      d.y_split_slope = 0.1f;
-      d.y_split_format = yfmt;
-      d.no_y = 1;
-      int s = sat_conv1d_f32(&d, x, h->convs[0].w, nullptr, stream);
-      if (s != SAT_OK) return s;
-    }
-    int C = h->c0, Tc = T;
-    const int nk = h->n_rbk();
-    int f8_mask = 0;
-    for (int i = 0; i < h->n_ups(); ++i) {
-      const int u = h->up_rates[i], k = h->up_kernels[i];
-      const int Cn = C / 2, Tn = Tc * u;
-      const bool last_stage = i == h->n_ups() - 1;
-      // this stage's ResBlock convs with 8-bit cross terms (SAT_CONV_F16F8R): the one-launch-per-conv path of the thick stages, every
-      // conv's second packing installed, and a batch the ring kernel would serve anyway (small batches keep the f16x3 tiles)
-      bool use_f8 = ((h->f8_stages >> i) & 1) && h->multi_branch && planes_res_all && !(side && i < h->branch_streams) && nk >= 2 && nk <= 3 &&
-                    Cn > 64 && Cn % 32 == 0 && (h->force_f8 || convring_wanted(Cn, Tn, B));
-      for (int j = 0; j < nk && use_f8; ++j)
-        for (int pair = 0; pair < 3; ++pair)
-          use_f8 = use_f8 && h->convs[h->id_rb(i, j, pair, 0)].w8 && h->convs[h->id_rb(i, j, pair, 1)].w8 &&
-                   (h->rb_kernels[j] - 1) * h->rb_dil[j * 3 + pair] <= 64 && h->rb_kernels[j] >= 3;
-      // ... and every descriptor of the stage asked of the ring kernel itself (convring_supports has more conditions than
-      // convring_wanted — 31-bit output slabs for the fast epilogue, an even step count, ...): a stage one of whose convs it would
-      // refuse keeps the f16x3 packing, whose dispatch has the register-staged tiles to fall back on (round-5 advisor item)
-      for (int j = 0; j < nk && use_f8; ++j)
-        for (int pair = 0; pair < 3 && use_f8; ++pair)
-          for (int which = 0; which < 2 && use_f8; ++which) {
-            const int rk = h->rb_kernels[j], dil = which ? 1 : h->rb_dil[j * 3 + pair];
-            const auto& cv = h->convs[h->id_rb(i, j, pair, which)];
-            sat_conv1d_desc d = base_desc(Cn, Cn, Tn, Tn, 1);
-            d.ksize = rk, d.dilation = dil, d.pad_left = (rk * dil - dil) / 2;
-            d.bias = cv.bias, d.w_descale = cv.descale, d.mode = SAT_CONV_F16F8R;
-            d.x_split = ws, d.x_split8 = ws, d.y_split = ws, d.y_split8 = ws, d.y_split_slope = 0.1f;   // (placeholders: nothing is launched)
-            d.no_y = 1;
-            if (which) {
-              d.in_lrelu = 1, d.in_slope = 0.1f, d.res_split = ws, d.res_split_slope = 0.1f, d.res_scale = 1.f;
-              if (pair == 2) d.no_y = 0, d.accum = j > 0, d.accum_div = j == nk - 1 ? (float)nk : 0.f, d.y_split8 = nullptr, d.y_split = (j == nk - 1 && !last_stage) ? ws : nullptr;
-            } else {
-              d.y_split_hi_only = 1;
-            }
-            use_f8 = sat_conv1d_f8r_supported(&d) != 0;
-          }
-      if (use_f8) f8_mask |= 1 << i;
-      // 8-bit (e5m2) sidecars (half a slot each: 2 bytes per element) in the slots of the f32 twins this pipeline does not write
-      void* Hs8 = ws + 0 * slot;
-      auto br8 = [&](int j, int which) { return ws + (size_t)(5 + j * 5 + (which < 2 ? 1 : 3)) * slot + (which == 1 ? slot / 2 : 0); };   // 0 T1, 1 RA, 2 RB
-      {
-        int lo, hi;
-        phase_window(k, u, (k - u) / 2, &lo, &hi);
-        sat_conv1d_desc d = base_desc(C, Cn, Tc, Tc, u);
-        d.ksize = hi - lo + 1;
-        d.pad_left = -lo;
-        d.bias = h->convs[h->id_up(i)].bias;
-        d.w_descale = h->convs[h->id_up(i)].descale;
-        d.mode = cmode;
-        d.x_split = XS;
-        // rates 2 and 4: the transposed conv writes the split planes itself (LDS-transposed epilogue); other
-        // rates (5: a block's 64 rows are not whole channel groups) store f32 and split in a streaming pass
-        const int co_b = Cn * u > 32 ? 64 : 32;
-        const bool direct = cmode == SAT_CONV_F16X3 && h->planes_residual && co_b % (8 * u) == 0;
-        int s;
-        if (h->ups2 && cmode == SAT_CONV_F16X3 && h->planes_residual && sat_upsample2_supported(C, k, u, (k - u) / 2)) {
-          s = sat_upsample2_f16x3(XS, h->convs[h->id_up(i)].w, h->convs[h->id_up(i)].bias, h->convs[h->id_up(i)].descale, Hs, 0.1f, B, C, Tc, stream);
-          if (s != SAT_OK) return s;
-        } else if (h->ups_ring && sat_upsample_grouped_supported(C, Cn, k, u, (k - u) / 2)) {
-          // rows grouped by phase (the packer consulted the same rule): the LDS-DMA ring, zero tap slots skipped (conv_ring16.hip)
-          if (!(cmode == SAT_CONV_F16X3 && h->planes_residual)) {
-            set_error("hifigan: option ups_ring (packed rows of the stride-4 upsamplers grouped by phase) needs split-f16 weights and the split-plane pipeline");
-            return SAT_ERR_INVALID;
-          }
-          d.y_split = Hs;
-          d.y_split_slope = 0.1f;
-          d.no_y = 1;
-          d.up_grouped = 1;
-          d.up_zero_taps = sat_convtranspose_zero_taps(k, u, (k - u) / 2);
-          if (use_f8) d.y_split8 = Hs8;        // the ring's upsampler epilogue writes the sidecar next to the planes
-          s = sat_conv1d_f32(&d, nullptr, h->convs[h->id_up(i)].w, nullptr, stream);
-          if (s != SAT_OK) return s;
-        } else if (direct) {
-          d.y_split = Hs;
-          d.y_split_slope = 0.1f;
-          d.no_y = 1;
-          s = sat_conv1d_f32(&d, nullptr, h->convs[h->id_up(i)].w, nullptr, stream);
-          if (s != SAT_OK) return s;
-        } else {
-          s = sat_conv1d_f32(&d, nullptr, h->convs[h->id_up(i)].w, Hf, stream);
-          if (s != SAT_OK) return s;
-          s = sat_act_split_f32(Hf, Hs, B, Cn, Tn, 0.1f, cmode == SAT_CONV_F16F8 ? SAT_SPLIT_F8 : SAT_SPLIT_F16, stream);
-          if (s != SAT_OK) return s;
-        }
-        if (use_f8 && !d.y_split8) {
-          s = sat_planes_f8_sidecar(Hs, Hs8, B, Cn, Tn, stream);      // (Hf is dead behind the split pass)
-          if (s != SAT_OK) return s;
-        }
-        if (h->range_probe) {
-          s = planes_range_probe(Hs, B, Cn, Tn, h->range_probe + 2 * i, stream);
-          if (s != SAT_OK) return s;
-        }
-      }
-      if (h->fuse_mrf && planes_res_all && h->fuse_pairs && nk <= 3 &&
-          sat_resblock_mrf_supported(Cn, nk, h->rb_kernels.data(), h->rb_dil.data()) &&
-          sat_resblock_mrf_scratch_bytes(nk, h->rb_kernels.data()) <= WS_MRF_SCRATCH) {
-        // the whole MRF block of this stage in one launch (mrf.hip): same bits as the loop below
-        sat_mrf_desc m{};
-        m.B = B; m.C = Cn; m.T = Tn; m.n_branches = nk;
-        for (int j = 0; j < nk; ++j) {
-          m.ksize[j] = h->rb_kernels[j];
-          for (int pair = 0; pair < 3; ++pair) {
-            m.dilation[j][pair] = h->rb_dil[j * 3 + pair];
-            for (int which = 0; which < 2; ++which) {
-              m.w[j][pair][which] = h->convs[h->id_rb(i, j, pair, which)].w;
-              m.bias[j][pair][which] = h->convs[h->id_rb(i, j, pair, which)].bias;
-              m.w_descale[j][pair][which] = h->convs[h->id_rb(i, j, pair, which)].descale;
-            }
-          }
-        }
-        m.slope = 0.1f;
-        m.x_split = Hs;
-        m.y = ACCf;
-        m.y_split = last_stage ? nullptr : XSn;
-        m.y_split_slope = 0.1f;
-        m.out_div = (float)nk;
-        m.residual_from_planes = !h->mrf_exact;
-        m.scratch = ws + (size_t)WS_SLOTS * slot;
-        m.scratch_bytes = WS_MRF_SCRATCH;
-        int s = sat_resblock_mrf_f16x3(&m, stream);
-        if (s != SAT_OK) return s;
-        void* t = XS;
-        XS = XSn;
-        XSn = t;
-        C = Cn;
-        Tc = Tn;
-        continue;
-      }
-      // The thick stages (no fused ResBlock step: C > 64): the i-th conv of ALL branches in one launch
-      // (sat_conv1d_multi_f32: the LDS-DMA ring kernel walks the tiles of the three kernel sizes; the MRF sum is
-      // accumulated branch by branch inside a block, in the order of the loop below) — 6 launches per stage instead of 18.
-      {
-        const bool planes_res = cmode == SAT_CONV_F16X3 && h->planes_residual;
-        const bool fan = side && i < h->branch_streams;
-        if (h->multi_branch && planes_res && !fan && nk >= 2 && nk <= 3 && Cn > 64) {
-          const float* xnull[3] = {nullptr, nullptr, nullptr};
-          const void* rs[3] = {Hs, Hs, Hs};
-          const void* rs8[3] = {Hs8, Hs8, Hs8};
-          for (int pair = 0; pair < 3; ++pair) {
-            sat_conv1d_desc d1[3], d2[3];
-            const void* w1[3];
-            const void* w2[3];
-            float* y1[3] = {nullptr, nullptr, nullptr};
-            float* y2[3];
-            void* dst_s[3];
-            void* dst8[3] = {nullptr, nullptr, nullptr};
-            for (int j = 0; j < nk; ++j) {
-              const int rk = h->rb_kernels[j], dil = h->rb_dil[j * 3 + pair];
-              const auto& cv1 = h->convs[h->id_rb(i, j, pair, 0)];
-              const auto& cv2 = h->convs[h->id_rb(i, j, pair, 1)];
-              void* T1s = br(j, 0);
-              void* RAs = br(j, 2);
-              void* RBs = br(j, 4);
-              d1[j] = base_desc(Cn, Cn, Tn, Tn, 1);
-              d1[j].ksize = rk;
-              d1[j].dilation = dil;
-              d1[j].pad_left = (rk * dil - dil) / 2;
-              d1[j].bias = cv1.bias;
-              d1[j].w_descale = cv1.descale;
-              d1[j].mode = cmode;
-              d1[j].x_split = rs[j];
-              d1[j].y_split = T1s;
-              d1[j].y_split_slope = 0.1f;
-              d1[j].no_y = 1;
-              w1[j] = cv1.w;
-              if (use_f8) {
-                d1[j].mode = SAT_CONV_F16F8R;
-                d1[j].x_split8 = rs8[j];
-                d1[j].y_split8 = br8(j, 0);
-                d1[j].y_split_hi_only = 1;          // the inner activation is only ever a matrix operand
-                w1[j] = cv1.w8;
-              }
-              d2[j] = base_desc(Cn, Cn, Tn, Tn, 1);
-              d2[j].ksize = rk;
-              d2[j].dilation = 1;
-              d2[j].pad_left = (rk - 1) / 2;
-              d2[j].in_lrelu = 1;
-              d2[j].in_slope = 0.1f;
-              d2[j].bias = cv2.bias;
-              d2[j].w_descale = cv2.descale;
-              d2[j].mode = cmode;
-              d2[j].res_split = rs[j];
-              d2[j].res_split_slope = 0.1f;
-              d2[j].res_scale = 1.f;
-              d2[j].y_split_slope = 0.1f;
-              d2[j].x_split = T1s;
-              if (pair < 2) {
-                dst_s[j] = (rs[j] == RAs) ? RBs : RAs;
-                d2[j].no_y = 1;
-                y2[j] = nullptr;
-              } else {
-                y2[j] = ACCf;
-                d2[j].accum = j > 0;
-                d2[j].accum_div = (j == nk - 1) ? (float)nk : 0.f;
-                dst_s[j] = (j == nk - 1 && !last_stage) ? XSn : nullptr;
-                // the mean only leaves this stage as planes (the next upsampler's input): its f32 form is not written
-                d2[j].accum_no_store = h->skip_dead_sum && j > 0 && dst_s[j] != nullptr;
-              }
-              d2[j].y_split = dst_s[j];
-              w2[j] = cv2.w;
-              if (use_f8) {
-                d2[j].mode = SAT_CONV_F16F8R;
-                d2[j].x_split8 = br8(j, 0);
-                if (pair < 2) dst8[j] = (rs8[j] == br8(j, 1)) ? br8(j, 2) : br8(j, 1), d2[j].y_split8 = dst8[j];
-                w2[j] = cv2.w8;
-              }
-            }
-            int s = sat_conv1d_multi_f32(d1, xnull, w1, y1, nk, stream);
-            if (s != SAT_OK) return s;
-            s = sat_conv1d_multi_f32(d2, xnull, w2, y2, nk, stream);
-            if (s != SAT_OK) return s;
-            for (int j = 0; j < nk && h->range_probe; ++j) {
-              s = planes_range_probe(br(j, 0), B, Cn, Tn, h->range_probe + 2 * i, stream);
-              if (s == SAT_OK && dst_s[j]) s = planes_range_probe(dst_s[j], B, Cn, Tn, h->range_probe + 2 * i, stream);
-              if (s != SAT_OK) return s;
-            }
-            for (int j = 0; j < nk; ++j) rs[j] = dst_s[j], rs8[j] = dst8[j];
-          }
-          void* t = XS;
-          XS = XSn;
-          XSn = t;
-          C = Cn;
-          Tc = Tn;
-          continue;
-        }
-      }
-      if (side && i < h->branch_streams) {
-        SAT_HIP(hipEventRecord(side->fork, (hipStream_t)stream));
-        for (auto st : side->s) SAT_HIP(hipStreamWaitEvent(st, side->fork, 0));
-      }
-      for (int j = 0; j < nk; ++j) {
-        const int rk = h->rb_kernels[j];
-        // branch j on its own stream (the last, longest branch on the caller's); sum order kept by events
-        const bool fan = side && i < h->branch_streams;   // option value = number of leading stages fanned out
-        void* stream_j = fan && j < 2 ? (void*)side->s[j] : stream;
-        void* T1s = br(j, 0);
-        float* RAf = (float*)br(j, 1);  void* RAs = br(j, 2);
-        float* RBf = (float*)br(j, 3);  void* RBs = br(j, 4);
-        const float* rf = Hf;
-        const void* rs = Hs;
-        for (int pair = 0; pair < 3; ++pair) {
-          const int dil = h->rb_dil[j * 3 + pair];
-          const auto& cv1 = h->convs[h->id_rb(i, j, pair, 0)];
-          const auto& cv2 = h->convs[h->id_rb(i, j, pair, 1)];
-          sat_conv1d_desc d2 = base_desc(Cn, Cn, Tn, Tn, 1);
-          d2.ksize = rk;
-          d2.dilation = 1;
-          d2.pad_left = (rk - 1) / 2;
-          d2.in_lrelu = 1;
-          d2.in_slope = 0.1f;
-          d2.bias = cv2.bias;
-          d2.w_descale = cv2.descale;
-          d2.mode = cmode;
-          // the residual is the pair's input: from its split planes (hi + lo, leaky-relu undone) when the
-          // format carries both halves, so no f32 copy of the activations is written inside a resblock
-          const bool planes_res = cmode == SAT_CONV_F16X3 && h->planes_residual;
-          if (planes_res) {
-            d2.res_split = rs;
-            d2.res_split_slope = 0.1f;
-          } else {
-            d2.res = rf;
-            d2.res_cstride = Tn;
-            d2.res_bstride = (int64_t)Cn * Tn;
-          }
-          d2.res_scale = 1.f;
-          d2.y_split_slope = 0.1f;
-          float* dstf;
-          void* dsts;
-          if (pair < 2) {
-            dstf = (rf == RAf) ? RBf : RAf;
-            dsts = (rs == RAs) ? RBs : RAs;
-            d2.no_y = planes_res;
-          } else {
-            dstf = ACCf;
-            d2.accum = j > 0;
-            d2.accum_div = (j == nk - 1) ? (float)nk : 0.f;
-            dsts = (j == nk - 1 && !last_stage) ? XSn : nullptr;   // the next stage's input planes
-            d2.accum_no_store = h->skip_dead_sum && planes_res && j > 0 && dsts != nullptr;      // (see the thick stages above)
-          }
-          d2.y_split = dsts;
-          int s;
-          // the MRF sum is read-modify-write on ACC: branch j's last kernel waits for branch j-1's
-          auto wait_prev_sum = [&]() -> int {
-            if (fan && pair == 2 && j > 0) SAT_HIP(hipStreamWaitEvent((hipStream_t)stream_j, side->acc[j - 1], 0));
-            return SAT_OK;
-          };
-          if ((Cn <= 32 || (Cn == 64 && planes_res && (h->fuse_pair64 & (rk == 3 ? 1 : rk == 7 ? 2 : 4)))) && h->fuse_pairs && cmode == SAT_CONV_F16X3) {
-            sat_conv1d_desc df = d2;
-            df.dilation = dil;
-            df.x_split = rs;
-            s = wait_prev_sum();
-            if (s != SAT_OK) return s;
-            s = sat_resblock_pair_scaled_f16x3(&df, planes_res ? nullptr : rf, cv1.w, cv1.bias, cv1.descale, cv2.w, dstf, stream_j);
-            if (s != SAT_OK) return s;
-          } else {
-            sat_conv1d_desc d1 = base_desc(Cn, Cn, Tn, Tn, 1);
-            d1.ksize = rk;
-            d1.dilation = dil;
-            d1.pad_left = (rk * dil - dil) / 2;
-            d1.bias = cv1.bias;
-            d1.w_descale = cv1.descale;
-            d1.mode = cmode;
-            d1.x_split = rs;
-            d1.y_split = T1s;
-            d1.y_split_slope = 0.1f;
-            d1.no_y = 1;
-            s = sat_conv1d_f32(&d1, nullptr, cv1.w, nullptr, stream_j);
-            if (s != SAT_OK) return s;
-            d2.x_split = T1s;
-            s = wait_prev_sum();
-            if (s != SAT_OK) return s;
-            s = sat_conv1d_f32(&d2, nullptr, cv2.w, dstf, stream_j);
-            if (s != SAT_OK) return s;
-          }
-          if (fan && pair == 2) SAT_HIP(hipEventRecord(side->acc[j], (hipStream_t)stream_j));
-          rf = dstf;
-          rs = dsts;
-        }
-      }
-      void* t = XS;
-      XS = XSn;
-      XSn = t;
-      C = Cn;
-      Tc = Tn;
-    }
-    h->last_f8_stages.store(f8_mask, std::memory_order_relaxed);
-    return sat_hifigan_convpost_f32(ACCf, (const float*)h->convs[h->id_post()].w, h->convs[h->id_post()].bias, y, B, C, Tc, stream);
-  }
+  fwd_ctx c = {h, B, stream, (char*)workspace, align_up(hifigan_max_elems(h, B, T) * sizeof(float), 256)};
+  if (hifigan_split_acts(h)) return forward_planes(c, x, y, T);
   h->last_f8_stages.store(0, std::memory_order_relaxed);
-
-  // conv_pre (archi.py:78)
-  {
-    sat_conv1d_desc d = base_desc(h->in_ch, h->c0, T, T, 1);
-    d.ksize = 7;
-    d.pad_left = 3;
-    d.bias = h->convs[0].bias;
-    d.w_descale = h->convs[0].descale;
-    d.mode = h->convs[0].mode;
-    int s = sat_conv1d_f32(&d, x, h->convs[0].w, X, stream);
-    if (s != SAT_OK) return s;
-  }
-  int C = h->c0;
-  int Tc = T;
-  const int nk = h->n_rbk();
-  for (int i = 0; i < h->n_ups(); ++i) {
-    const int u = h->up_rates[i], k = h->up_kernels[i];
-    const int Cn = C / 2, Tn = Tc * u;
-    // x = leaky_relu(x, 0.1); x = ups[i](x)   (archi.py:80-81)
-    {
-      int lo, hi;
-      phase_window(k, u, (k - u) / 2, &lo, &hi);
-      if (h->ups_ring && sat_upsample_grouped_supported(C, Cn, k, u, (k - u) / 2)) {
-        set_error("hifigan: option ups_ring (packed rows of the stride-4 upsamplers grouped by phase) needs the split-plane pipeline (split_acts)");
-        return SAT_ERR_INVALID;
-      }
-      sat_conv1d_desc d = base_desc(C, Cn, Tc, Tc, u);
-      d.ksize = hi - lo + 1;
-      d.pad_left = -lo;
-      d.in_lrelu = 1;
-      d.in_slope = 0.1f;
-      d.bias = h->convs[h->id_up(i)].bias;
-      d.w_descale = h->convs[h->id_up(i)].descale;
-      d.mode = h->convs[h->id_up(i)].mode;
-      int s = sat_conv1d_f32(&d, X, h->convs[h->id_up(i)].w, H, stream);
-      if (s != SAT_OK) return s;
-    }
-    // xs = sum_j resblock_j(x); x = xs / num_kernels   (archi.py:82-86)
-    for (int j = 0; j < nk; ++j) {
-      const int rk = h->rb_kernels[j];
-      const float* r = H;
-      for (int pair = 0; pair < 3; ++pair) {
-        const int dil = h->rb_dil[j * 3 + pair];
-        const auto& cv1 = h->convs[h->id_rb(i, j, pair, 0)];
-        const auto& cv2 = h->convs[h->id_rb(i, j, pair, 1)];
-        float* dst;
-        // x = c2(leaky_relu(xt, 0.1)) + x with xt = c1(leaky_relu(x, 0.1))
-        sat_conv1d_desc d2 = base_desc(Cn, Cn, Tn, Tn, 1);
-        d2.ksize = rk;
-        d2.dilation = 1;
-        d2.pad_left = (rk - 1) / 2;
-        d2.in_lrelu = 1;
-        d2.in_slope = 0.1f;
-        d2.bias = cv2.bias;
-        d2.w_descale = cv2.descale;
-        d2.mode = cv2.mode;
-        d2.res = r;
-        d2.res_scale = 1.f;
-        d2.res_cstride = Tn;
-        d2.res_bstride = (int64_t)Cn * Tn;
-        if (pair < 2) {
-          dst = (r == RA) ? RB : RA;
-        } else {
-          dst = ACC;  // xs += resblock(x); the last one also divides by num_kernels
-          d2.accum = j > 0;
-          d2.accum_div = (j == nk - 1) ? (float)nk : 0.f;
-        }
-        int s;
-        if (Cn <= 32 && Cn % 16 == 0 && cv1.mode == SAT_CONV_F16X3 && cv2.mode == SAT_CONV_F16X3 && h->fuse_pairs) {
-          // thin stages sit on the HBM roofline: one fused kernel, the intermediate stays in LDS
-          sat_conv1d_desc df = d2;
-          df.dilation = dil;
-          s = sat_resblock_pair_scaled_f16x3(&df, r, cv1.w, cv1.bias, cv1.descale, cv2.w, dst, stream);
-          if (s != SAT_OK) return s;
-        } else {
-          sat_conv1d_desc d1 = base_desc(Cn, Cn, Tn, Tn, 1);
-          d1.ksize = rk;
-          d1.dilation = dil;
-          d1.pad_left = (rk * dil - dil) / 2;
-          d1.in_lrelu = 1;
-          d1.in_slope = 0.1f;
-          d1.bias = cv1.bias;
-          d1.w_descale = cv1.descale;
-          d1.mode = cv1.mode;
-          s = sat_conv1d_f32(&d1, r, cv1.w, T1, stream);
-          if (s != SAT_OK) return s;
-          s = sat_conv1d_f32(&d2, T1, cv2.w, dst, stream);
-          if (s != SAT_OK) return s;
-        }
-        r = dst;
-      }
-    }
-    float* t = X;
-    X = ACC;
-    ACC = t;
-    C = Cn;
-    Tc = Tn;
-  }
-  // x = leaky_relu(x); reflection_pad; conv_post; tanh   (archi.py:87-90)
-  return sat_hifigan_convpost_f32(X, (const float*)h->convs[h->id_post()].w, h->convs[h->id_post()].bias, y, B, C, Tc, stream);
+  return forward_handover(c, x, y, T);
 }

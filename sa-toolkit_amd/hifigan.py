@@ -61,6 +61,9 @@ class CoreHifiGan(CoreHifiGanParams):
     #: "f16f8r" at EVERY batch size (the calibration batch of Net.check_precision is too small for the ring kernel's default dispatch)
     force_f8 = 0
 
+    #: the attributes above that the packed weights and the C handle's options depend on (_param_key), in the handle's option names
+    _OPTIONS = ("split_acts", "branch_streams", "fuse_pair64", "fuse_mrf", "ups2", "multi_branch", "ups_ring", "f8_stages", "skip_dead_sum")
+
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self._handle = None
@@ -75,7 +78,7 @@ class CoreHifiGan(CoreHifiGanParams):
         ps = self.__dict__.get("_flat_params")
         if ps is None:
             ps = self.__dict__["_flat_params"] = list(self.parameters())
-        return (self.precision, self.split_acts, self.branch_streams, self.fuse_pair64, self.fuse_mrf, self.ups2, self.multi_branch, self.ups_ring, self.f8_stages, self.skip_dead_sum) + tuple((p.data_ptr(), p._version) for p in ps)
+        return (self.precision,) + tuple(getattr(self, n) for n in self._OPTIONS) + tuple((p.data_ptr(), p._version) for p in ps)
 
     def invalidate(self):
         self._packed_key = None
@@ -162,17 +165,8 @@ class CoreHifiGan(CoreHifiGanParams):
                     raise _lib.SatError(f"generator conv {i}: split-f16 packed weights without .w_descale (lost by .to() / .clone(): "
                                         "use packing.move_packed, or set it to 1.0 for weights packed with scale=False)")
                 check(l.sat_hifigan_set_conv_descale(self._handle, i, float(wp.w_descale)), "sat_hifigan_set_conv_descale")
-        check(l.sat_hifigan_set_option(self._handle, b"split_acts", int(self.split_acts)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"branch_streams", int(self.branch_streams)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"fuse_pair64", int(self.fuse_pair64)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"fuse_mrf", int(self.fuse_mrf)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"multi_branch", int(self.multi_branch)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"ups2", int(self.ups2)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"force_f8", int(self.force_f8)), "sat_hifigan_set_option")
-        check(l.sat_hifigan_set_option(self._handle, b"skip_dead_sum", int(self.skip_dead_sum)), "sat_hifigan_set_option")
         # (a frozen model brings the row order its weights were packed in)
         self._packed_ups_grouped = self._ups_grouped() if ups_grouped is None else bool(ups_grouped)
-        check(l.sat_hifigan_set_option(self._handle, b"ups_ring", int(self._packed_ups_grouped)), "sat_hifigan_set_option")
         # second packings (SAT_CONV_F16F8R) of the thick stages' ResBlock convs: {conv id: packed tensor}
         packed8 = dict(packed8 or {})
         stages = 0
@@ -180,7 +174,10 @@ class CoreHifiGan(CoreHifiGanParams):
         for i, w8 in packed8.items():
             check(l.sat_hifigan_set_conv_f8r(self._handle, int(i), ptr(w8)), "sat_hifigan_set_conv_f8r")
             stages |= 1 << ((int(i) - 1 - n_ups) // (6 * nk))
-        check(l.sat_hifigan_set_option(self._handle, b"f8_stages", stages & int(self.f8_stages)), "sat_hifigan_set_option")
+        # the handle's options: the attributes, but what was packed where the handle must follow the packing
+        packed_as = {"ups_ring": int(self._packed_ups_grouped), "f8_stages": stages & int(self.f8_stages)}
+        for name in self._OPTIONS + ("force_f8",):
+            check(l.sat_hifigan_set_option(self._handle, name.encode(), packed_as.get(name, int(getattr(self, name)))), "sat_hifigan_set_option")
         self._packed8 = packed8
         self._packed = packed  # keeps the device buffers alive
         self._packed_modes = list(modes)

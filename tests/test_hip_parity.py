@@ -683,6 +683,70 @@ def _split_plane_pipeline_equals_f32_handover(g, x, lib, check):
     assert rms((y2 - y1).cpu().numpy()) < 5e-7
 
 
+# single-option deviations of the C handle and what each does to the waveform of 2 x 25 frames against the default options: None = the same
+# bits, a number = bar on the RMS difference.  fuse_mrf, multi_branch and skip_dead_sum are documented as "same bits" (csrc/hifigan.hip,
+# hifigan.py); the relation of the others was measured before the forward was split into functions (profiles/hifigan_option_paths.txt):
+# a bar is 4 x the measured RMS (room for another seed, not for another accumulation) and never above 5e-7, this file's bar for
+# "another accumulation order"
+_OPTION_PATHS = {
+    # deviation: (f16x3 + ring, f16x3 on the register-staged tiles, f16f8r forced)
+    ("fuse_mrf", 0): (None, None, None),
+    ("multi_branch", 0): (None, None, "skip"),      # (switches the 8-bit terms off by design)
+    ("skip_dead_sum", 0): (None, None, None),
+    ("ups2", 0): (4 * 8.418e-8, 4 * 8.426e-8, 4 * 8.390e-8),
+    ("fuse_pair64", 0): (None, None, None),
+    ("fuse_pair64", 7): (None, None, None),
+    ("fuse_pairs", 0): (4 * 6.453e-8, 4 * 6.516e-8, 4 * 6.510e-8),
+    ("mrf_exact", 1): (4 * 7.006e-8, 4 * 7.058e-8, 4 * 7.060e-8),
+}
+
+
+def test_generator_option_paths_of_the_forward(model_f16x3):
+    """every branch of sat_hifigan_forward_f32 that an option of the handle selects, through a whole forward: one run per single-option
+    deviation against the default options (_OPTION_PATHS), with the thick stages on the three-job ring launch, on the register-staged
+    tiles, and as SAT_CONV_F16F8R"""
+    import ctypes
+    from satools_amd._lib import lib, check
+    g = model_f16x3.hifigan
+    x = torch.randn(2, g.imput_dim, 25, generator=torch.Generator().manual_seed(3)).to(DEV)
+
+    def run_setting(col, name, f8r):
+        def forward():
+            y = g(x)[0].clone()
+            if f8r:
+                assert g.last_arithmetic == "f16f8r(stages 1,2)", g.last_arithmetic
+            return y
+        y_def = forward()
+        for (opt, value), bars in _OPTION_PATHS.items():
+            bar = bars[col]
+            if bar == "skip":
+                continue
+            keep = ctypes.c_int(0)
+            check(lib().sat_hifigan_get_option(g._handle, opt.encode(), ctypes.byref(keep)), "get_option")
+            assert keep.value != value, (opt, value)
+            check(lib().sat_hifigan_set_option(g._handle, opt.encode(), value), "set_option")
+            try:
+                y = forward()
+            finally:
+                check(lib().sat_hifigan_set_option(g._handle, opt.encode(), keep.value), "set_option")
+            same, err = torch.equal(y, y_def), rms((y - y_def).cpu().numpy())
+            print(f"option paths [{name}] {opt} = {value}: {'same bits' if same else 'rms %.3e' % err}")
+            assert same if bar is None else err < bar, (name, opt, value, err)
+        assert torch.equal(forward(), y_def)          # every option back where it was
+
+    with conv_option("convring", 33, 1):
+        run_setting(0, "f16x3 ring", False)
+    with conv_option("convring", 0, 1):
+        run_setting(1, "f16x3 tiles", False)
+    g.precision = "f16f8r"            # (model_f16x3 restores the precision)
+    g.invalidate()
+    g.set_force_f8(1)
+    try:
+        run_setting(2, "f16f8r", True)
+    finally:
+        g.set_force_f8(0)
+
+
 # ---------------------------------------------------------------------------------------------
 # generator and end to end
 # ---------------------------------------------------------------------------------------------
