@@ -192,6 +192,17 @@ _PROTOS_CONV2D16 = {
     "sat_conv2d_f16x3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
 }
 
+# include/satools_hip_ragged.h (csrc/ragged/): a fourth table, bound like the other three
+_I32P = C.POINTER(C.c_int32)
+_PROTOS_RAGGED = {
+    "sat_melspec_logmel_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, _I32P] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+    "sat_instnorm_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "sat_row_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "sat_se_gate_add_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_int64, C.c_void_p]),
+    "sat_attentive_stats_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
+    "sat_res2_chain_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 8 + [C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -210,6 +221,11 @@ def conv2d16_symbols():
     return sorted(_PROTOS_CONV2D16)
 
 
+def ragged_symbols():
+    """names declared in include/satools_hip_ragged.h that the library must export"""
+    return sorted(_PROTOS_RAGGED)
+
+
 def library_path():
     """where the in-tree shared library lives (built by sa-toolkit_amd/build.py)"""
     return LIB_PATH
@@ -224,7 +240,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python sa-toolkit_amd/build.py` "
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items()):
             try:
                 fn = getattr(l, name)
             except AttributeError:

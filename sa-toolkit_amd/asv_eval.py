@@ -22,6 +22,7 @@ the ROCCH segment that crosses the diagonal, and `eer_lower` / `eer_upper` are N
 `eer_ci` (`asv-eval --eer-ci M`) the three come from `eer_interval` instead: the empirical EER of the calibrated LLRs and the percentile
 interval of M bootstrap replicates of it, drawn and counted on the device (ops.eer_bootstrap, csrc/stats/eer_bootstrap.hip)."""
 import json
+import logging
 import os
 
 import numpy as np
@@ -327,20 +328,13 @@ def compute_metrics(utt2embd_enroll, utt2embd_trial, enroll_spk2utt, trials_file
     return metrics
 
 
-def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_file, out_dir, as_norm=True, eer_ci=None):
-    """objf.py:189-266: extract, score, measure.  Writes `<out_dir>/xvectors.npz` (`utts`, `xvectors`), `scores` and `metric.json`
-    and returns the metric dict.  One utterance per extractor call, as the reference (the kernels take no per-utterance lengths,
-    and zero padding would change the InstanceNorm and the pooling); an utterance of both lists is extracted once.
-    eer_ci: see `score_metrics`."""
-    from .pipeline import load_wav_from_scp, read_wav_scp
-    model.eval()
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        raise _lib.SatError("x-vector extraction runs on the HIP device only: move the model there first (no CPU fallback)")
-    enroll_scp, trials_scp = read_wav_scp(enroll_wav_scp), read_wav_scp(trials_wav_scp)
-    spk2utt = {}
-    for u, s in read_wav_scp(enroll_utt2spk).items():
-        spk2utt.setdefault(s, []).append(u)
+_logged_no_batch = set()
+
+
+def extract_xvectors(model, enroll_scp, trials_scp, device, batch_size=1, max_frames=65536):
+    """the extraction step of `test_metrics`: two {utterance: scp entry} dicts -> two {utterance: x-vector [D]} dicts in their order; an
+    utterance of both lists is extracted once.  batch_size = 1, or a model without `extract_batch`: `model(wav)` per utterance."""
+    from .pipeline import load_wav_from_scp
 
     def extract(entry):
         wav, _sr = load_wav_from_scp(entry)
@@ -348,8 +342,59 @@ def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_f
             _, xv = model(wav.squeeze().to(device), target=None)
         return xv.reshape(-1)
 
-    enroll = {u: extract(e) for u, e in enroll_scp.items()}
-    trial = {u: enroll[u] if u in enroll else extract(e) for u, e in trials_scp.items()}
+    batched = int(batch_size) > 1 and hasattr(model, "extract_batch")
+    if int(batch_size) > 1 and not batched and type(model).__qualname__ not in _logged_no_batch:
+        _logged_no_batch.add(type(model).__qualname__)
+        logging.getLogger(__name__).warning("batch_size = %d: this extractor has no extract_batch, one utterance per call", int(batch_size))
+    if not batched:
+        enroll = {u: extract(e) for u, e in enroll_scp.items()}
+        return enroll, {u: enroll[u] if u in enroll else extract(e) for u, e in trials_scp.items()}
+    # scp order, up to batch_size utterances and up to max_frames frames per call (a longer utterance is a call of its own); the samples
+    # of one group at a time are in host memory
+    todo = list(enroll_scp.items()) + [(u, e) for u, e in trials_scp.items() if u not in enroll_scp]
+    vec, group, total = {}, [], 0
+
+    def flush():
+        with torch.no_grad():
+            xv = model.extract_batch([w.to(device) for _, w in group])
+        for row, (u, _) in enumerate(group):
+            vec[u] = xv[row].reshape(-1)
+
+    for u, e in todo:
+        wav = load_wav_from_scp(e)[0].reshape(-1)
+        frames = 1 + int(wav.shape[0]) // 160
+        if group and (len(group) >= int(batch_size) or total + frames > int(max_frames)):
+            flush()
+            group, total = [], 0
+        group.append((u, wav))
+        total += frames
+    if group:
+        flush()
+    return {u: vec[u] for u in enroll_scp}, {u: vec[u] for u in trials_scp}
+
+
+def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_file, out_dir, as_norm=True, eer_ci=None, batch_size=1,
+                 max_frames=65536):
+    """objf.py:189-266: extract, score, measure.  Writes `<out_dir>/xvectors.npz` (`utts`, `xvectors`), `scores` and `metric.json`
+    and returns the metric dict.  batch_size = 1: one utterance per extractor call, as the reference (the row kernels take no
+    per-utterance lengths, and zero padding would change the InstanceNorm and the pooling).  batch_size = N > 1 with a model that has
+    `extract_batch` (the ECAPA-TDNN net): the utterances, in scp order, go N at a time — and at most `max_frames` frames at a time: a
+    1 536-channel buffer of 65 536 frames is 403 MB — through one ragged call each (xvector.Net.extract_batch); a model without it
+    extracts one per call and says so once.  An utterance of both lists is extracted once either way.
+    eer_ci: see `score_metrics`."""
+    from .pipeline import read_wav_scp
+    model.eval()
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise _lib.SatError("x-vector extraction runs on the HIP device only: move the model there first (no CPU fallback)")
+    if int(batch_size) < 1 or int(max_frames) < 1:
+        raise _lib.SatError(f"test_metrics: batch_size = {batch_size}, max_frames = {max_frames}: both at least 1")
+    enroll_scp, trials_scp = read_wav_scp(enroll_wav_scp), read_wav_scp(trials_wav_scp)
+    spk2utt = {}
+    for u, s in read_wav_scp(enroll_utt2spk).items():
+        spk2utt.setdefault(s, []).append(u)
+
+    enroll, trial = extract_xvectors(model, enroll_scp, trials_scp, device, batch_size=batch_size, max_frames=max_frames)
     cohort = None
     if as_norm and hasattr(model, "after_speaker_embedding"):
         cohort = torch.nn.functional.normalize(model.after_speaker_embedding.weight.data, dim=1)
@@ -398,7 +443,13 @@ def main(argv=None):
     ap.add_argument("--report", action="store_true", help="also print the two lines of the reference's report step (raw, AS-norm)")
     ap.add_argument("--resnet-conv2d", choices=("f32", "f16x3"), default=None,
                     help="arithmetic of the 2-D convs of the ResNet extractor's blocks (its conv2d_precision); an error for the ECAPA model")
+    ap.add_argument("--batch-size", type=int, default=1, metavar="N",
+                    help="utterances per extractor call: above 1 the ECAPA-TDNN model extracts ragged batches of up to N utterances of any lengths "
+                         "(the ResNet model has no such path and extracts one per call); 1 = one per call, the reference's way")
+    ap.add_argument("--max-frames", type=int, default=65536, metavar="F", help="most frames (10 ms each) in one ragged batch")
     a = ap.parse_args(argv)
+    if a.batch_size < 1 or a.max_frames < 1:
+        ap.error("--batch-size and --max-frames take positive counts")
     if a.eer_ci < 0:
         ap.error("--eer-ci takes a count of replicates (0 = off)")
     model = load_model(a.checkpoint).to(a.device)
@@ -407,7 +458,8 @@ def main(argv=None):
             ap.error("--resnet-conv2d: the loaded model is not the ResNet extractor (it has no 2-D convs)")
         model.conv2d_precision = a.resnet_conv2d
     ci = dict(m=a.eer_ci, ci=0.95, seed=a.eer_ci_seed) if a.eer_ci else None
-    m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm, eer_ci=ci)
+    m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm, eer_ci=ci,
+                     **({} if a.batch_size == 1 else dict(batch_size=a.batch_size, max_frames=a.max_frames)))
     print(json.dumps({k: v for k, v in m.items() if k != "score"}))
     if a.report:
         print("\n".join(report_lines(m)))

@@ -518,12 +518,9 @@ def melspec_logmel(wav, window, fb, coef=0.97):
     wav = _f32c(wav)
     B, n = wav.shape
     n_mel = fb.shape[0]
-    nz = fb > 0
-    lo = torch.where(nz.any(1), nz.float().argmax(1), torch.zeros(n_mel, dtype=torch.long, device=fb.device)).to(torch.int32)
-    hi = torch.where(nz.any(1), fb.shape[1] - torch.flip(nz, [1]).float().argmax(1),
-                     torch.zeros(n_mel, dtype=torch.long, device=fb.device)).to(torch.int32)
+    lo, hi = mel_filter_ranges(fb)
     out = torch.empty(B, n_mel, 1 + n // 160, dtype=torch.float32, device=wav.device)
-    check(lib().sat_melspec_logmel_f32(ptr(wav), ptr(out), ptr(window), ptr(fb), ptr(lo.contiguous()), ptr(hi.contiguous()), B, n,
+    check(lib().sat_melspec_logmel_f32(ptr(wav), ptr(out), ptr(window), ptr(fb), ptr(lo), ptr(hi), B, n,
                                        n_mel, float(coef), stream()), "sat_melspec_logmel_f32")
     return out
 
@@ -899,3 +896,194 @@ def row_mean_std(x):
     out = torch.empty(B, 2 * c, dtype=torch.float32, device=x.device)
     check(lib().sat_row_mean_std_f32(ptr(x), ptr(out), B, c, t, stream()), "sat_row_mean_std_f32")
     return out
+
+
+# ---- ragged batches of the x-vector extractor (csrc/ragged/, include/satools_hip_ragged.h) ---------------------------------------
+RAGGED_GAP, RAGGED_ALIGN, RAGGED_MAX_SEGMENTS = 2, 4, 1024
+XV_HOP, XV_MIN_SAMPLES = 160, 513             # csrc/xvector.hip: frames = 1 + n // 160; the reflect padding needs n > 512
+
+
+def ragged_layout(frames):
+    """the packed time axis of a ragged batch (include/satools_hip_ragged.h): frames [B] -> (seg_off [B], seg_len [B], T_tot), int32 numpy.
+    off_0 = 0, off_{i+1} = round_up(off_i + T_i + 2, 4), T_tot = off_B: at least 2 gap columns after every segment, the last included,
+    every segment on a multiple of 4 columns.  Pure host code."""
+    import numpy as np
+    frames = [int(t) for t in frames]
+    if not frames or len(frames) > RAGGED_MAX_SEGMENTS or min(frames) < 1:
+        raise _lib.SatError(f"ragged_layout: 1 .. {RAGGED_MAX_SEGMENTS} segments of at least one frame each, got {len(frames)}"
+                            + (f" with a segment of {min(frames)}" if frames else ""))
+    off, pos = [], 0
+    for t in frames:
+        off.append(pos)
+        pos = -(-(pos + t + RAGGED_GAP) // RAGGED_ALIGN) * RAGGED_ALIGN
+    if pos >= 2 ** 31:
+        raise _lib.SatError("ragged_layout: 2^31 columns or more")
+    return np.asarray(off, dtype=np.int32), np.asarray(frames, dtype=np.int32), pos
+
+
+def ragged_tiles(frames):
+    """the tile table of sat_res2_chain_segments_f32: int32 pairs (segment, first column inside it) for 64-column centres, then for
+    128-column centres -> (tiles [n64 + n128, 2], n64, n128)"""
+    import numpy as np
+    pairs = [(i, t0) for centre in (64, 128) for i, t in enumerate(frames) for t0 in range(0, int(t), centre)]
+    n64 = sum(-(-int(t) // 64) for t in frames)
+    return np.asarray(pairs, dtype=np.int32).reshape(-1, 2), n64, len(pairs) - n64
+
+
+class _PinnedRing:
+    """page-locked int32 blocks for the tables of ragged batches, reused in turn (f0._PinnedInts explains why not `pin_memory()` per call).
+    A block is written again SLOTS uploads later, after the event behind its last copy: a host that runs that far ahead waits for a copy
+    issued four batches ago, never for a kernel."""
+    SLOTS = 4
+
+    def __init__(self):
+        import threading
+        self.slots, self.next, self.lock = [None] * self.SLOTS, 0, threading.Lock()
+
+    def upload(self, words, device):
+        """int32 numpy vector -> device tensor, one asynchronous copy on the current stream"""
+        n = int(words.size)
+        with self.lock:
+            k, self.next = self.next, (self.next + 1) % self.SLOTS
+            slot = self.slots[k]
+            if slot is not None:
+                slot[1].synchronize()
+            if slot is None or slot[0].numel() < n:
+                slot = [torch.empty(max(n, 8192), dtype=torch.int32, pin_memory=True), None]
+            slot[0][:n].copy_(torch.from_numpy(words))
+            dev = torch.empty(n, dtype=torch.int32, device=device)
+            dev.copy_(slot[0][:n], non_blocking=True)
+            slot[1] = torch.cuda.Event()
+            slot[1].record(torch.cuda.current_stream(device))
+            self.slots[k] = slot
+        return dev
+
+
+_ragged_ring = _PinnedRing()
+
+
+class RaggedTable:
+    """the tables of one ragged batch: built on the host from the known lengths, on the device after ONE copy.
+    `n_samples` [B] (frames = 1 + n // 160) or `frames` [B] alone (for the kernels past the front end)"""
+
+    def __init__(self, device, n_samples=None, frames=None):
+        import numpy as np
+        if n_samples is not None:
+            n_samples = [int(n) for n in n_samples]
+            frames = [1 + max(n, 0) // XV_HOP for n in n_samples]
+        else:
+            frames = [int(t) for t in frames]
+            n_samples = [(t - 1) * XV_HOP for t in frames]
+        off, length, self.T_tot = ragged_layout(frames)
+        tiles, self.n_tiles64, self.n_tiles128 = ragged_tiles(frames)
+        self.B, self.frames, self.n_samples_list = len(frames), frames, n_samples
+        self.host_off, self.host_len = off, length
+        self.n_samples_host = (C.c_int32 * self.B)(*n_samples)
+        B = self.B
+        dev = _ragged_ring.upload(np.concatenate([off, length, np.asarray(n_samples, dtype=np.int32), tiles.reshape(-1)]), device)
+        self.seg_off, self.seg_len, self.n_samples, self.tiles = dev[:B], dev[B:2 * B], dev[2 * B:3 * B], dev[3 * B:]
+
+    def segment(self, x, i):
+        """the columns of segment i of a packed tensor [..., T_tot]"""
+        return x[..., int(self.host_off[i]):int(self.host_off[i]) + int(self.host_len[i])]
+
+
+def _packed2(t, tab, what):
+    """[1, C, T_tot] or [C, T_tot] f32 on the device -> (C, the tensor made contiguous)"""
+    t = _f32c(t)
+    if t.dim() == 3 and t.shape[0] == 1:
+        c = t.shape[1]
+    elif t.dim() == 2:
+        c = t.shape[0]
+    else:
+        raise _lib.SatError(f"{what}: a packed tensor is [1, C, T_tot] or [C, T_tot], got {tuple(t.shape)}")
+    if t.shape[-1] != tab.T_tot:
+        raise _lib.SatError(f"{what}: {t.shape[-1]} columns, the table has T_tot = {tab.T_tot}")
+    return c, t
+
+
+def mel_filter_ranges(fb):
+    """first and one-past-last nonzero bin of every filter of fb [n_mel, 513] -> (lo, hi) int32 on fb's device: the bins the kernels' mel dot
+    products run over"""
+    n_mel = fb.shape[0]
+    nz = fb > 0
+    lo = torch.where(nz.any(1), nz.float().argmax(1), torch.zeros(n_mel, dtype=torch.long, device=fb.device)).to(torch.int32)
+    hi = torch.where(nz.any(1), fb.shape[1] - torch.flip(nz, [1]).float().argmax(1),
+                     torch.zeros(n_mel, dtype=torch.long, device=fb.device)).to(torch.int32)
+    return lo.contiguous(), hi.contiguous()
+
+
+def melspec_logmel_segments(wav, tab, window, fb, coef=0.97, fb_range=None):
+    """wav [B, n_max] (anything past n_i) -> log-mel [1, n_mel, T_tot], utterance i at its own length in segment i; gap columns unwritten"""
+    wav = _f32c(wav)
+    if wav.dim() != 2 or wav.shape[0] != tab.B:
+        raise _lib.SatError(f"melspec_logmel_segments: wav {tuple(wav.shape)} against a table of {tab.B} utterances")
+    B, n_max = wav.shape
+    n_mel = fb.shape[0]
+    lo, hi = fb_range if fb_range is not None else mel_filter_ranges(fb)
+    out = torch.empty(1, n_mel, tab.T_tot, dtype=torch.float32, device=wav.device)
+    check(lib().sat_melspec_logmel_segments_f32(ptr(wav), ptr(tab.n_samples), tab.n_samples_host, ptr(tab.seg_off), ptr(tab.seg_len), ptr(out),
+                                                ptr(window), ptr(fb), ptr(lo), ptr(hi), B, n_max, tab.T_tot, n_mel, float(coef), stream()),
+          "sat_melspec_logmel_segments_f32")
+    return out
+
+
+def instnorm_segments(x, tab, eps=1e-5, out=None):
+    """InstanceNorm per (row, segment) of a packed tensor; the gap columns of the result are zeros"""
+    c, x = _packed2(x, tab, "instnorm_segments")
+    y = torch.empty_like(x) if out is None else out
+    check(lib().sat_instnorm_segments_f32(ptr(x), ptr(y), ptr(tab.seg_off), ptr(tab.seg_len), c, tab.B, tab.T_tot, float(eps), stream()),
+          "sat_instnorm_segments_f32")
+    return y
+
+
+def row_mean_segments(x, tab):
+    """packed [1, C, T_tot] -> [B, C]: mean over each segment"""
+    c, x = _packed2(x, tab, "row_mean_segments")
+    y = torch.empty(tab.B, c, dtype=torch.float32, device=x.device)
+    check(lib().sat_row_mean_segments_f32(ptr(x), ptr(y), ptr(tab.seg_off), ptr(tab.seg_len), c, tab.B, tab.T_tot, stream()),
+          "sat_row_mean_segments_f32")
+    return y
+
+
+def se_gate_add_segments(z, gate_logits, skips, tab, out=None):
+    """z * sigmoid(gate_logits[i, c]) + skips[0] + skips[1] + ... on the columns of segment i (up to three skips, left to right); `out` may be a
+    channel slice of a wider packed tensor; its gap columns are not written"""
+    c, z = _packed2(z, tab, "se_gate_add_segments")
+    g = _f32c(gate_logits.reshape(tab.B, c))
+    sk = [_packed2(s, tab, "se_gate_add_segments")[1] for s in skips] + [None] * (3 - len(skips))
+    if out is None:
+        out = torch.empty_like(z)
+    if out.shape[-2:] != z.shape[-2:] or out.stride(-1) != 1 or out.numel() != z.numel():
+        raise _lib.SatError(f"se_gate_add_segments: out {tuple(out.shape)} for z {tuple(z.shape)}")
+    check(lib().sat_se_gate_add_segments_f32(ptr(z), ptr(g), ptr(sk[0]), ptr(sk[1]), ptr(sk[2]), ptr(out, strided=True), ptr(tab.seg_off),
+                                             ptr(tab.seg_len), c, tab.B, tab.T_tot, out.stride(-2), stream()), "sat_se_gate_add_segments_f32")
+    return out
+
+
+def attentive_stats_segments(x, logits, tab):
+    """packed x, logits [1, C, T_tot] -> [B, 2C]: softmax-weighted mean and std over each segment"""
+    c, x = _packed2(x, tab, "attentive_stats_segments")
+    c2, logits = _packed2(logits, tab, "attentive_stats_segments")
+    if c2 != c:
+        raise _lib.SatError("attentive_stats_segments: x and logits of different channel counts")
+    out = torch.empty(tab.B, 2 * c, dtype=torch.float32, device=x.device)
+    check(lib().sat_attentive_stats_segments_f32(ptr(x), ptr(logits), ptr(out), ptr(tab.seg_off), ptr(tab.seg_len), c, tab.B, tab.T_tot, stream()),
+          "sat_attentive_stats_segments_f32")
+    return out
+
+
+def res2_chain_segments(y, w, scale, shift, dilation, tab, centre=0, out=None):
+    """ops.res2_chain with every segment of the packed y [1, (nums + 1) * 64, T_tot] an utterance of its own; centre = 0 (automatic), 64 or
+    128 columns per block.  Gap columns of the result are not written."""
+    C_, y = _packed2(y, tab, "res2_chain_segments")
+    nums = w.shape[0]
+    if tuple(w.shape) != (nums, 3, 64, 64) or tuple(scale.shape) != (nums, 64) or tuple(shift.shape) != (nums, 64) or C_ != (nums + 1) * 64:
+        raise _lib.SatError(f"res2_chain_segments: w {tuple(w.shape)} / scale {tuple(scale.shape)} do not fit y {tuple(y.shape)}")
+    z = torch.empty_like(y) if out is None else out
+    if z.shape != y.shape or not z.is_contiguous() or z.data_ptr() == y.data_ptr():
+        raise _lib.SatError("res2_chain_segments: `out` must be a contiguous tensor of y's shape, not y itself")
+    check(lib().sat_res2_chain_segments_f32(ptr(y), ptr(z), ptr(_f32c(w)), ptr(_f32c(scale)), ptr(_f32c(shift)), ptr(tab.seg_off), ptr(tab.seg_len),
+                                            ptr(tab.tiles), tab.n_tiles64, tab.n_tiles128, tab.B, C_, tab.T_tot, nums, int(dilation), int(centre),
+                                            stream()), "sat_res2_chain_segments_f32")
+    return z

@@ -9,6 +9,8 @@ L2-normalised 192-dim embedding — computed on the HIP kernels:
               Res2Net partial sums, SE gate (+ the block's skip connections)   add3_kernel, se_gate_add_kernel
   pooling     tanh, softmax over time + weighted mean / std                    tanh_kernel, attentive_stats_kernel
   head        Linear(3072 -> 192) + BatchNorm on the conv kernel, L2 norm      l2norm_rows_kernel
+  ragged      `extract_batch`: utterances of unequal length on one packed     csrc/ragged/xvector_ragged.hip, the segment forms of
+              time axis, the convs unchanged                                   the front end, norm, chain, SE mean / gate, pooling
 
 The parameter tree carries the reference's state-dict keys (torchaudio's `MelSpec.spectrogram.window` /
 `mel_scale.fb` buffers included), so a reference checkpoint loads with `load_state_dict`.  No CPU fallback."""
@@ -126,6 +128,7 @@ def build(args=None):
             self.stat_pooling = _AttentiveStatsPool(1536, 128)
             self.after_speaker_embedding = _ArcMargin(self.embedding_size, num_speakers)
             self._cache, self._cache_key = None, None
+            self._mel_ranges = None
             super().eval()
 
         def train(self, mode=True):
@@ -234,6 +237,84 @@ def build(args=None):
             pooled = ops.attentive_stats(h, logits)                                 # [B, 2 * 3C, 1]
             e = ops.linear_rows(pooled, W["emb"]["w"], ch_scale=W["emb"]["scale"], ch_shift=W["emb"]["shift"])
             return ops.l2norm_rows(e.reshape(B, self.embedding_size))
+
+        # ---- ragged batches (csrc/ragged/, include/satools_hip_ragged.h) --------------------------------
+        def _block_segments(self, x, blk, dil, skips, out, tab):
+            """`_block` on the packed time axis: the chain, the SE mean and the gate per segment, the 1x1 convs on all columns"""
+            y = self._crb(x, blk["in"])
+            z_in = ops.res2_chain_segments(y, blk["chain"]["w"], blk["chain"]["scale"], blk["chain"]["shift"], dil, tab)
+            z = self._crb(z_in, blk["out"])
+            m = ops.row_mean_segments(z, tab)                                      # [B, C]
+            g = ops.linear_rows(m, blk["se1_w"], bias=blk["se1_b"], relu=True)
+            g = ops.linear_rows(g, blk["se2_w"], bias=blk["se2_b"])
+            return ops.se_gate_add_segments(z, g, skips, tab, out=out)
+
+        def embed_segments(self, feats, tab):
+            """`embed` of a packed feature tensor [1, 80, T_tot] (gap columns zero) -> [B, 192].  Gap columns of every intermediate hold
+            anything: the convs that touch them are pointwise in time, and the segment kernels never read them."""
+            W = self._prepare(feats.device)
+            out1 = self._crb(feats, W["layer1"], pad=2)
+            _, C, T = out1.shape
+            cat = torch.empty(1, 3 * C, T, dtype=torch.float32, device=feats.device)
+            out2 = self._block_segments(out1, W["blocks"][0], 2, [out1], cat[:, :C], tab)
+            out3 = self._block_segments(ops.add3(out1, out2), W["blocks"][1], 3, [out1, out2], cat[:, C:2 * C], tab)
+            self._block_segments(ops.add3(out1, out2, out3), W["blocks"][2], 4, [out1, out2, out3], cat[:, 2 * C:], tab)
+            h = ops.conv1d(cat, W["cat"]["w"], 3 * C, 1, bias=W["cat"]["b"], relu=True, mode=W["mode1"])
+            a = ops.tanh_(ops.conv1d(h, W["asp1"]["w"], 128, 1, bias=W["asp1"]["b"], mode=W["mode1"]))
+            logits = ops.conv1d(a, W["asp2"]["w"], 3 * C, 1, bias=W["asp2"]["b"], mode=W["mode1"])
+            pooled = ops.attentive_stats_segments(h, logits, tab)                   # [B, 2 * 3C]
+            # A NaN or an infinity among an utterance's samples makes its whole feature segment NaN (the InstanceNorm's mean), and the
+            # reference's ReLU would carry that to the x-vector.  The conv epilogue's ReLU is max(v, 0), which gives 0 for NaN: the NaNs
+            # would end after layer1 and a broken utterance would come out as a plausible vector.  So the segment's NaN is carried past
+            # the body: 0 * (sum of the feature rows' means) is 0 for a finite segment and NaN otherwise, added to the pooled row.
+            pooled = pooled + ops.row_mean_segments(feats, tab).sum(1, keepdim=True) * 0.0
+            e = ops.linear_rows(pooled, W["emb"]["w"], ch_scale=W["emb"]["scale"], ch_shift=W["emb"]["shift"])
+            return ops.l2norm_rows(e)
+
+        def extract_batch(self, wavs):
+            """x-vectors of a RAGGED batch in one launch sequence: `wavs` = a list of 1-D device tensors of any lengths, or
+            (padded [B, n_max], lengths) with anything past each length and `lengths` a list or a CPU tensor -> [B, 192], row i the L2-normalised x-vector of utterance i
+            at its own length (what `forward` gives for it alone, to f32 rounding) — and all NaN for an utterance with a NaN or an infinite
+            sample, as the reference's arithmetic gives it (`forward` returns a finite vector there: its ReLUs drop the NaNs).  The utterances lie side by side on one packed time
+            axis (ops.ragged_layout); the tables are built on the host from the lengths and uploaded once; nothing waits for the device.
+            Needs the fused Res2Net chain; at most 1024 utterances and 1536 * T_tot * 4 < 2^31 bytes per call."""
+            if isinstance(wavs, tuple) and len(wavs) == 2 and isinstance(wavs[0], torch.Tensor) and wavs[0].dim() == 2:
+                padded, lengths = wavs
+                lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+                if len(lengths) != padded.shape[0] or (lengths and max(lengths) > padded.shape[1]):
+                    raise _lib.SatError(f"extract_batch: {len(lengths)} lengths up to {max(lengths, default=0)} for a padded batch {tuple(padded.shape)}")
+                tensors = [padded]
+            else:
+                tensors = list(wavs)
+                if any(not isinstance(w, torch.Tensor) or w.dim() != 1 for w in tensors):
+                    raise _lib.SatError("extract_batch: a list of 1-D tensors, or (padded [B, n_max], lengths)")
+                lengths, padded = [int(w.shape[0]) for w in tensors], None
+            if not lengths:
+                raise _lib.SatError("extract_batch: an empty batch")
+            if any(not w.is_cuda for w in tensors):
+                raise _lib.SatError("x-vector extraction runs on the HIP device only (no CPU fallback)")
+            if len(lengths) > ops.RAGGED_MAX_SEGMENTS:
+                raise _lib.SatError(f"extract_batch: {len(lengths)} utterances in one call, at most {ops.RAGGED_MAX_SEGMENTS}")
+            for i, n in enumerate(lengths):
+                if n < ops.XV_MIN_SAMPLES:
+                    raise _lib.SatError(f"extract_batch: utterance {i} of {n} samples is shorter than the reflect padding ({ops.XV_MIN_SAMPLES} samples)")
+            device = tensors[0].device
+            W = self._prepare(device)
+            if not self.res2_chain or any(b["chain"] is None for b in W["blocks"]):
+                raise _lib.SatError("extract_batch needs the fused Res2Net chain (res2_chain = True, 64-channel three-tap pieces): "
+                                    "without it, extract one utterance per call")
+            t_tot = ops.ragged_layout([1 + n // ops.XV_HOP for n in lengths])[2]
+            if 1536 * t_tot * 4 >= 2 ** 31:
+                raise _lib.SatError(f"extract_batch: {t_tot} frames in one call, a 1536-channel buffer of 2^31 bytes or more: split the batch")
+            if padded is None:
+                padded = tensors[0].to(torch.float32).unsqueeze(0) if len(tensors) == 1 else \
+                    torch.nn.utils.rnn.pad_sequence([w.to(torch.float32) for w in tensors], batch_first=True)
+            padded = padded.to(torch.float32).contiguous()
+            tab = ops.RaggedTable(device, n_samples=lengths)
+            if self._mel_ranges is None or self._mel_ranges[0] is not W:
+                self._mel_ranges = (W, ops.mel_filter_ranges(W["fb"]))
+            mel = ops.melspec_logmel_segments(padded, tab, W["window"], W["fb"], W["coef"], fb_range=self._mel_ranges[1])
+            return self.embed_segments(ops.instnorm_segments(mel, tab, out=mel), tab)
 
         def forward(self, x, target=None):
             if target is not None:
