@@ -526,7 +526,8 @@ int sat_yaapt_ragged_f32(const sat_yaapt_plan* plan, const float* wav, const int
  * party to the reference, restated in oracle/wav2vec2.py).  All matrix-shaped work (conv feature
  * extractor after layer 0, Linear layers, grouped positional conv, attention products) goes through
  * sat_conv1d_f32; these are the remaining pieces.
- *   sat_w2v2_conv0_f32:        y[b][c][t] = bias[c] + sum_j w[c][j] x[b][t*stride + j]
+ *   sat_w2v2_conv0_f32:        y[b][c][t] = bias[c] + sum_j w[c][j] x[b][t*stride + j]; C <= 1024, k <= 16 and the weights
+ *                              and the bias within 64 KB of LDS: (C k + C) * 4 <= 65536, SAT_ERR_INVALID before a launch beyond
  *   sat_layernorm_channels_f32: LayerNorm over C of x[B][C][T] (eps 1e-5), optional erf-GELU; with
  *                              split_phases the output is [B][2C][ceil(T/2)] = even | odd time phases,
  *                              which turns the next stride-2 conv into a stride-1 conv

@@ -92,7 +92,32 @@ __device__ __forceinline__ float erf_fast(float x) {
   s = s * x;
   return ax < 0.6f ? s : big;
 }
-__device__ __forceinline__ float gelu_fast(float v) { return v * 0.5f * (1.0f + erf_fast(v * 0.70710678118654752440f)); }
+// GELU on erf_fast's two branches.  Above |z| = 0.6 it is formed from 1 - erf(|z|) = q e itself — v - (v / 2) q e for v >= 0, (v / 2) q e
+// below — and not as v / 2 * (1 + erf): that form rounds 1 - q e, 1 + erf and the product one after the other, and at |v| ~ 3, where
+// the Abramowitz-Stegun error is largest, the three roundings took the result to 4.7e-7 from float64 (tests/test_ref64_w2v2.py); this
+// one rounds once, in the fma: 3.4e-7.  (v = +inf gives NaN here, inf before; -inf gave NaN in both.)
+__device__ __forceinline__ float gelu_fast(float v) {
+  const float x = v * 0.70710678118654752440f;
+  const float ax = __builtin_fabsf(x);
+  const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, ax, 1.0f));
+  float q = __builtin_fmaf(1.061405429f, t, -1.453152027f);
+  q = __builtin_fmaf(q, t, 1.421413741f);
+  q = __builtin_fmaf(q, t, -0.284496736f);
+  q = __builtin_fmaf(q, t, 0.254829592f);
+  q = q * t;
+  const float x2 = x * x;
+  const float e = __builtin_amdgcn_exp2f(x2 * -1.4426950408889634f);
+  const float qe = q * e;                          // 1 - erf(|x|)
+  const float h = v * 0.5f;
+  const float big = v >= 0.f ? __builtin_fmaf(-h, qe, v) : h * qe;
+  float s = __builtin_fmaf(-0.0008548327023450853f, x2, 0.005223977625442188f);
+  s = __builtin_fmaf(s, x2, -0.026866170645131252f);
+  s = __builtin_fmaf(s, x2, 0.11283791670955126f);
+  s = __builtin_fmaf(s, x2, -0.37612638903183754f);
+  s = __builtin_fmaf(s, x2, 1.1283791670955126f);
+  s = s * x;
+  return ax < 0.6f ? h * (1.0f + s) : big;
+}
 
 // GELU of four values at once for the exposed epilogues of the GEMM kernels (32 M GELUs per 1024 -> 4096 launch: 37 of its
 // 204 us with gelu_fast): the Abramowitz-Stegun branch alone — GELU multiplies 1 + erf by x / 2, so the RELATIVE accuracy of

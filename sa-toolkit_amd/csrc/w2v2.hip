@@ -9,7 +9,7 @@ namespace sat {
 
 __device__ __forceinline__ float gelu_erf(float v) { return gelu_fast(v); }
 
-// y[b][c][t] = bias[c] + sum_j w[c][j] * x[b][t*stride + j]      (C <= 512, k <= 16)
+// y[b][c][t] = bias[c] + sum_j w[c][j] * x[b][t*stride + j]      (C <= 1024, k <= 16, (C k + C) * 4 bytes <= 64 KB of LDS)
 __global__ void __launch_bounds__(256) w2v2_conv0_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bias, float* __restrict__ y, int n,
                                                         int C, int k, int stride, int T) {
@@ -253,6 +253,7 @@ __global__ void __launch_bounds__(1024) softmax_cols_kernel(float* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int AT_P_SCALE_LOG2 = 10;   // the softmax weights are split as P 2^10: the largest is 1024, far below the 65504 of f16
 constexpr int AT_VU = 33;       // LDS row pitch of the split V image in 16-byte units: rows 4 banks apart -> conflict-free 16-byte reads
 
 __device__ __forceinline__ void split8(const float (&a)[8], h8& hi, h8& lo) {
@@ -404,7 +405,12 @@ __global__ void __launch_bounds__(64 * NW, 1) attention_f16x3_kernel(const uint4
       for (int r = 0; r < 16; ++r) mr = fmaxf(mr, st[m][r]);
     }
     mr = fmaxf(mr, __shfl_xor(mr, 32));
-    const float mx = fmaxf(m_run, mr * scale2);               // running maximum in units of log2
+    // The weights are kept as P 2^AT_P_SCALE_LOG2: the running "maximum" sits that many binades below the true one.  The lo half of a
+    // split weight below 2^-3 is an f16 subnormal, a multiple of 2^-24 cut toward zero, and with the largest weight at 1 those cuts — all
+    // of one sign, up to 2^-24 |v| per key — add up over the keys (measured: 2.9e-5 of O at 700 frames under one dominant key).  With
+    // the largest weight at 2^10 a cut is at most 2^-34 of it.  l_run sums the same scaled weights, alpha is a ratio of two offsets that
+    // carry the same shift, and 1 / l_run takes the factor out again.
+    const float mx = fmaxf(m_run, mr * scale2 - (float)AT_P_SCALE_LOG2);       // running maximum in units of log2, shifted
     const float alpha = __builtin_amdgcn_exp2f(m_run - mx);   // 0 on the first block (m_run = -inf); v_exp_f32, 1 ulp
     float sum = 0.f;
 #pragma unroll
@@ -546,6 +552,8 @@ extern "C" int sat_w2v2_conv0_f32(const float* x, const float* w, const float* b
   SAT_REQUIRE(B > 0 && C > 0 && C <= 1024 && k >= 1 && k <= 16 && stride >= 1 && n >= k, "w2v2_conv0: unsupported shape");
   const int T = (n - k) / stride + 1;
   const size_t lds = ((size_t)C * k + C) * sizeof(float);
+  // the weights and the bias sit in dynamic LDS, launched without a larger-LDS attribute: the default 64 KB is the limit
+  SAT_REQUIRE(lds <= 65536, "w2v2_conv0: %d channels x %d taps need %zu bytes of LDS for the weights and the bias (at most 65536)", C, k, lds);
   dim3 grid(ceil_div(T, 256), B);
   hipLaunchKernelGGL(w2v2_conv0_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, y, n, C, k, stride, T);
   SAT_LAUNCH_CHECK("w2v2_conv0_kernel");
