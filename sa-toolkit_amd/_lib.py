@@ -203,6 +203,14 @@ _PROTOS_RAGGED = {
     "sat_res2_chain_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 8 + [C.c_void_p]),
 }
 
+# include/satools_hip_ragged2d.h (csrc/ragged2d/): a fifth table, bound like the other four
+_PROTOS_RAGGED2D = {
+    "sat_conv2d_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
+    "sat_plane_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "sat_se_scale_add_relu_segments_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
+    "sat_row_mean_std_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -226,6 +234,11 @@ def ragged_symbols():
     return sorted(_PROTOS_RAGGED)
 
 
+def ragged2d_symbols():
+    """names declared in include/satools_hip_ragged2d.h that the library must export"""
+    return sorted(_PROTOS_RAGGED2D)
+
+
 def library_path():
     """where the in-tree shared library lives (built by sa-toolkit_amd/build.py)"""
     return LIB_PATH
@@ -240,7 +253,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python sa-toolkit_amd/build.py` "
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items()):
+        for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items())
+                                  + list(_PROTOS_RAGGED2D.items())):
             try:
                 fn = getattr(l, name)
             except AttributeError:

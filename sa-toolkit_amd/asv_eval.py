@@ -333,7 +333,8 @@ _logged_no_batch = set()
 
 def extract_xvectors(model, enroll_scp, trials_scp, device, batch_size=1, max_frames=65536):
     """the extraction step of `test_metrics`: two {utterance: scp entry} dicts -> two {utterance: x-vector [D]} dicts in their order; an
-    utterance of both lists is extracted once.  batch_size = 1, or a model without `extract_batch`: `model(wav)` per utterance."""
+    utterance of both lists is extracted once.  batch_size = 1, or a model without `extract_batch`: `model(wav)` per utterance; otherwise
+    ragged groups through `model.extract_batch` (both extractors of this package have it)."""
     from .pipeline import load_wav_from_scp
 
     def extract(entry):
@@ -378,8 +379,10 @@ def test_metrics(model, enroll_wav_scp, trials_wav_scp, enroll_utt2spk, trials_f
     """objf.py:189-266: extract, score, measure.  Writes `<out_dir>/xvectors.npz` (`utts`, `xvectors`), `scores` and `metric.json`
     and returns the metric dict.  batch_size = 1: one utterance per extractor call, as the reference (the row kernels take no
     per-utterance lengths, and zero padding would change the InstanceNorm and the pooling).  batch_size = N > 1 with a model that has
-    `extract_batch` (the ECAPA-TDNN net): the utterances, in scp order, go N at a time — and at most `max_frames` frames at a time: a
-    1 536-channel buffer of 65 536 frames is 403 MB — through one ragged call each (xvector.Net.extract_batch); a model without it
+    `extract_batch` (the ECAPA-TDNN net and the ResNet net): the utterances, in scp order, go N at a time — and at most `max_frames`
+    frames at a time — through one ragged call each (xvector.Net.extract_batch, xvector_resnet.Net.extract_batch).  Memory of a call:
+    the ECAPA net's 1 536-channel buffer of 65 536 frames is 403 MB; the ResNet's first images, [32][80][frames], are 10 KB per frame —
+    671 MB at 65 536 frames, several of them live at once: lower `max_frames` where that does not fit.  A model without `extract_batch`
     extracts one per call and says so once.  An utterance of both lists is extracted once either way.
     eer_ci: see `score_metrics`."""
     from .pipeline import read_wav_scp
@@ -444,9 +447,11 @@ def main(argv=None):
     ap.add_argument("--resnet-conv2d", choices=("f32", "f16x3"), default=None,
                     help="arithmetic of the 2-D convs of the ResNet extractor's blocks (its conv2d_precision); an error for the ECAPA model")
     ap.add_argument("--batch-size", type=int, default=1, metavar="N",
-                    help="utterances per extractor call: above 1 the ECAPA-TDNN model extracts ragged batches of up to N utterances of any lengths "
-                         "(the ResNet model has no such path and extracts one per call); 1 = one per call, the reference's way")
-    ap.add_argument("--max-frames", type=int, default=65536, metavar="F", help="most frames (10 ms each) in one ragged batch")
+                    help="utterances per extractor call: above 1 the model (ECAPA-TDNN or ResNet) extracts ragged batches of up to N utterances "
+                         "of any lengths; 1 = one per call, the reference's way")
+    ap.add_argument("--max-frames", type=int, default=65536, metavar="F",
+                    help="most frames (10 ms each) in one ragged batch; the ResNet model's largest tensors take 10 KB per frame (671 MB at the "
+                         "default, several live at once), the ECAPA-TDNN model's 6 KB")
     a = ap.parse_args(argv)
     if a.batch_size < 1 or a.max_frames < 1:
         ap.error("--batch-size and --max-frames take positive counts")

@@ -1087,3 +1087,144 @@ def res2_chain_segments(y, w, scale, shift, dilation, tab, centre=0, out=None):
                                             ptr(tab.tiles), tab.n_tiles64, tab.n_tiles128, tab.B, C_, tab.T_tot, nums, int(dilation), int(centre),
                                             stream()), "sat_res2_chain_segments_f32")
     return z
+
+
+# ---- ragged batches of the ResNet x-vector extractor (csrc/ragged2d/, include/satools_hip_ragged2d.h) ------------------------------
+RESNET_LEVELS = 4                             # time resolutions of the half-ResNet34: the stem and layer1, then one per stride-2 layer
+
+
+def ragged_levels(frames):
+    """the packed time axes of a ragged batch at the ResNet's four time resolutions (include/satools_hip_ragged2d.h): frames [B] ->
+    [(seg_off [B], seg_len [B], T_tot)] * 4, level l + 1 holding (T - 1) // 2 + 1 frames of every T of level l, each level laid out by
+    ragged_layout on its own.  Pure host code."""
+    levels, frames = [], [int(t) for t in frames]
+    for _ in range(RESNET_LEVELS):
+        levels.append(ragged_layout(frames))
+        frames = [(t - 1) // 2 + 1 for t in frames]
+    return levels
+
+
+def ragged_column_segments(off, length, t_tot):
+    """column -> segment of one packed axis, int32 [T_tot]: i on the columns of segment i; a gap column names the segment before it
+    (any valid row would do: nothing reads what is gathered there)"""
+    import numpy as np
+    return (np.searchsorted(np.asarray(off), np.arange(int(t_tot)), side="right") - 1).astype(np.int32)
+
+
+class RaggedLevel:
+    """one packed time axis: what the segment kernels need of a RaggedTable.  `off`, `length` int32 numpy [B] and T_tot; the device
+    copies are given (RaggedLevels: slices of its one upload) or made here (a table of one's own, a blocking copy)"""
+
+    def __init__(self, off, length, t_tot, seg_off=None, seg_len=None, device=None):
+        import numpy as np
+        off, length = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(length, dtype=np.int32)
+        if seg_off is None:
+            seg_off, seg_len = torch.from_numpy(off.copy()).to(device), torch.from_numpy(length.copy()).to(device)
+        self.host_off, self.host_len, self.T_tot, self.seg_off, self.seg_len = off, length, int(t_tot), seg_off, seg_len
+        self.B, self.frames = len(off), [int(n) for n in length]
+
+    segment = RaggedTable.segment
+
+
+class RaggedLevels:
+    """the tables of one ragged batch of the ResNet extractor, one per time resolution: built on the host from the known lengths, on the
+    device after ONE asynchronous copy (the ring of RaggedTable); nothing waits for the device.  `n_samples` [B] (frames = 1 + n // 160)
+    or `frames` [B] alone.  levels[0] serves wherever a RaggedTable does in the front end (melspec_logmel_segments, instnorm_segments);
+    `columns` is the column -> segment index of the last level (int32 [T_tot_3])."""
+
+    def __init__(self, device, n_samples=None, frames=None):
+        import numpy as np
+        if n_samples is not None:
+            n_samples = [int(n) for n in n_samples]
+            frames = [1 + max(n, 0) // XV_HOP for n in n_samples]
+        else:
+            frames = [int(t) for t in frames]
+            n_samples = [(t - 1) * XV_HOP for t in frames]
+        host = ragged_levels(frames)
+        B = self.B = len(frames)
+        col = ragged_column_segments(*host[-1])
+        dev = _ragged_ring.upload(np.concatenate([a for off, length, _ in host for a in (off, length)]
+                                                 + [np.asarray(n_samples, dtype=np.int32), col]), device)
+        self.levels = [RaggedLevel(off, length, t, dev[2 * l * B:(2 * l + 1) * B], dev[(2 * l + 1) * B:(2 * l + 2) * B])
+                       for l, (off, length, t) in enumerate(host)]
+        first = self.levels[0]
+        first.n_samples, first.n_samples_list, first.n_samples_host = dev[8 * B:9 * B], n_samples, (C.c_int32 * B)(*n_samples)
+        self.columns = dev[9 * B:]
+
+    def __getitem__(self, l):
+        return self.levels[l]
+
+
+def _packed3(t, tab, what):
+    """[1, C, H, T_tot] or [C, H, T_tot] f32 on the device -> (C, H, the tensor made contiguous)"""
+    t = _f32c(t)
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3:
+        raise _lib.SatError(f"{what}: a packed image is [1, C, H, T_tot] or [C, H, T_tot], got {tuple(t.shape)}")
+    if t.shape[-1] != tab.T_tot:
+        raise _lib.SatError(f"{what}: {t.shape[-1]} columns, the table has T_tot = {tab.T_tot}")
+    return t.shape[0], t.shape[1], t
+
+
+def conv2d_segments(x, w_packed, ksize, stride, tab_in, tab_out, ch_scale=None, ch_shift=None, relu=False, out=None):
+    """ops.conv2d with every segment of the packed image x [1, Cin, H, T_in] an utterance of its own -> [1, Cout, Ho, T_out]: segment i
+    of `tab_in` (W_i columns) goes to segment i of `tab_out`, which holds (W_i - 1) // stride + 1 columns (the same table at stride 1, the
+    next level's at stride 2; any table of those lengths does).  Gap columns of the result are not written."""
+    cin, H, x = _packed3(x, tab_in, "conv2d_segments")
+    if w_packed.dim() != 3 or w_packed.dtype != torch.float32 or not w_packed.is_contiguous():
+        raise _lib.SatError("conv2d_segments: packed weights [k * k, Cin, Cout] (pack_conv2d_weight) are needed")
+    taps, cin_w, cout = w_packed.shape
+    stride = int(stride)
+    if taps != ksize * ksize or cin_w != cin or stride < 1:
+        raise _lib.SatError(f"conv2d_segments: packed weights {tuple(w_packed.shape)} do not fit x {tuple(x.shape)} with ksize {ksize}, stride {stride}")
+    for t in (ch_scale, ch_shift):
+        if t is not None and (t.numel() != cout or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.SatError("conv2d_segments: ch_scale / ch_shift are contiguous f32 vectors of Cout values")
+    if tab_out.B != tab_in.B or [(n - 1) // stride + 1 for n in tab_in.frames] != tab_out.frames:
+        raise _lib.SatError(f"conv2d_segments: the output table's segments are not the input's at stride {stride}")
+    Ho = (H - 1) // stride + 1
+    y = torch.empty(1, cout, Ho, tab_out.T_tot, dtype=torch.float32, device=x.device) if out is None else out
+    if tuple(y.shape[-3:]) != (cout, Ho, tab_out.T_tot) or y.numel() != cout * Ho * tab_out.T_tot or y.dtype != torch.float32:
+        raise _lib.SatError(f"conv2d_segments: out {tuple(y.shape)} is not [1, {cout}, {Ho}, {tab_out.T_tot}]")
+    check(lib().sat_conv2d_segments_f32(ptr(x), ptr(w_packed), ptr(y), ptr(ch_scale), ptr(ch_shift), int(bool(relu)), ptr(tab_in.seg_off),
+                                        ptr(tab_in.seg_len), ptr(tab_out.seg_off), tab_in.B, max(tab_in.frames), cin, cout, H, tab_in.T_tot,
+                                        tab_out.T_tot, int(ksize), stride, stream()), "sat_conv2d_segments_f32")
+    return y
+
+
+def plane_mean_segments(x, tab):
+    """packed [1, C, H, T_tot] -> [B, C]: the mean over the H x T_i plane of each segment (the SE squeeze)"""
+    c, H, x = _packed3(x, tab, "plane_mean_segments")
+    y = torch.empty(tab.B, c, dtype=torch.float32, device=x.device)
+    check(lib().sat_plane_mean_segments_f32(ptr(x), ptr(y), ptr(tab.seg_off), ptr(tab.seg_len), c, H, tab.B, tab.T_tot, stream()),
+          "sat_plane_mean_segments_f32")
+    return y
+
+
+def se_scale_add_relu_segments(z, gate_logits, r, tab, out=None):
+    """relu(z * sigmoid(gate_logits[i, c]) + r) on the columns of segment i; z, r packed [1, C, H, T_tot]; gap columns of the result are
+    not written"""
+    c, H, z = _packed3(z, tab, "se_scale_add_relu_segments")
+    c2, H2, r = _packed3(r, tab, "se_scale_add_relu_segments")
+    if (c2, H2) != (c, H):
+        raise _lib.SatError(f"se_scale_add_relu_segments: z {tuple(z.shape)} and r {tuple(r.shape)} must be of one shape")
+    g = _f32c(gate_logits.reshape(tab.B, c))
+    y = torch.empty(1, c, H, tab.T_tot, dtype=torch.float32, device=z.device) if out is None else out
+    if y.numel() != z.numel() or y.dtype != torch.float32:
+        raise _lib.SatError(f"se_scale_add_relu_segments: out {tuple(y.shape)} for z {tuple(z.shape)}")
+    check(lib().sat_se_scale_add_relu_segments_f32(ptr(z), ptr(g), ptr(r), ptr(y), ptr(tab.seg_off), ptr(tab.seg_len), tab.B, max(tab.frames), c, H,
+                                                   tab.T_tot, stream()), "sat_se_scale_add_relu_segments_f32")
+    return y
+
+
+def row_mean_std_segments(x, tab):
+    """packed [1, R, T_tot] -> [B, 2R]: mean and unbiased standard deviation over each segment, means first.  A segment of one column has
+    no unbiased deviation and is refused"""
+    c, x = _packed2(x, tab, "row_mean_std_segments")
+    if min(tab.frames) < 2:
+        raise _lib.SatError(f"row_mean_std_segments: segment {tab.frames.index(min(tab.frames))} of {min(tab.frames)} column: the unbiased deviation needs two")
+    out = torch.empty(tab.B, 2 * c, dtype=torch.float32, device=x.device)
+    check(lib().sat_row_mean_std_segments_f32(ptr(x), ptr(out), ptr(tab.seg_off), ptr(tab.seg_len), c, tab.B, tab.T_tot, stream()),
+          "sat_row_mean_std_segments_f32")
+    return out

@@ -13,6 +13,8 @@ L2-normalised 256-dim embedding — computed on the HIP kernels:
               attention MLP (1x1 Conv1d on the fused conv kernel), tanh                 conv1d, tanh_kernel
               softmax over time + weighted mean / std at C = 2560                       attentive_stats_kernel
   head        Linear(5120 -> 256) + BatchNorm, L2 norm                                  linear_rows_kernel, l2norm_rows_kernel
+  ragged      `extract_batch`: utterances of unequal length side by side on one       csrc/ragged2d/resnet_ragged.hip, the segment forms of
+              packed time axis per time resolution, exact f32                          the conv, the squeeze, the tail and the context
 
 AXES.  The reference runs the ResNet on [B, 1, T, 80] images, frequency innermost (sidekit/archi.py:110-113), and permutes its
 [B, 256, T', 10] output to [B, 2560, T'] for the pooling (sidekit/pooling.py:126-128).  Here TIME stays innermost from the front end's
@@ -110,7 +112,7 @@ def build(args=None):
                 ("lin_be", nn.Linear(5120, self.embedding_size, bias=False)), ("bn_be", nn.BatchNorm1d(self.embedding_size))]))
             self.stat_pooling = _AttentivePooling(256, 10)
             self.after_speaker_embedding = _ArcMargin(self.embedding_size, num_speakers)
-            self._cache, self._cache_key = None, None
+            self._cache, self._cache_key, self._mel_ranges = None, None, None
             super().eval()
 
         def train(self, mode=True):
@@ -247,6 +249,98 @@ def build(args=None):
                 taps["pooled"] = pooled
             e = ops.linear_rows(pooled, W["emb"]["w"], ch_scale=W["emb"]["scale"], ch_shift=W["emb"]["shift"])
             return ops.l2norm_rows(e.reshape(B, self.embedding_size))
+
+        # ---- ragged batches (csrc/ragged2d/, include/satools_hip_ragged2d.h) ------------------------------
+        @staticmethod
+        def _conv_segments(x, e, tab_in, tab_out, relu=False):
+            return ops.conv2d_segments(x, e["w"], e["k"], e["s"], tab_in, tab_out, ch_scale=e["scale"], ch_shift=e["shift"], relu=relu)
+
+        def _block_segments(self, x, blk, tab_in, tab_out):
+            """`_block` on the packed images: conv1 and the shortcut go from the input's level to the output's (the same one at stride 1),
+            conv2, the squeeze and the tail stay on the output's; the SE layer's two Linear layers see [B, C] rows as in `_block`"""
+            out = self._conv_segments(self._conv_segments(x, blk["c1"], tab_in, tab_out, relu=True), blk["c2"], tab_out, tab_out)
+            m = ops.plane_mean_segments(out, tab_out)                               # [B, C]
+            g = ops.linear_rows(ops.linear_rows(m, blk["fc0"], relu=True), blk["fc2"])
+            r = x if blk["sc"] is None else self._conv_segments(x, blk["sc"], tab_in, tab_out)
+            return ops.se_scale_add_relu_segments(out, g, r, tab_out)
+
+        def embed_segments(self, feats, levels):
+            """`embed` of a packed feature tensor [1, 80, T_tot_0] -> [B, 256]; `levels` = the batch's ops.RaggedLevels.  The 2-D convs
+            run in exact f32 (csrc/ragged2d/; there is no segment form of the split-f16 kernel).  Gap columns of every intermediate hold
+            anything: the segment kernels never read them, and the attention's 1x1 convs are pointwise in time."""
+            W = self._prepare(feats.device)
+            self.last_conv2d_arithmetic = "f32"
+            x = self._conv_segments(feats.view(1, 1, feats.shape[-2], feats.shape[-1]), W["stem"], levels[0], levels[0], relu=True)
+            i, lvl = 0, 0
+            for li, n in enumerate(BLOCKS):
+                for j in range(n):
+                    nxt = lvl + 1 if (li > 0 and j == 0) else lvl
+                    x = self._block_segments(x, W["blocks"][i], levels[lvl], levels[nxt])
+                    i, lvl = i + 1, nxt
+            tab = levels[lvl]
+            x = x.view(1, x.shape[1] * x.shape[2], x.shape[3])                     # [1, 2560, T_tot_3]
+            a1, a2 = W["att1"], W["att2"]
+            gc = ops.row_mean_std_segments(x, tab)                                  # [B, 5120]
+            ctx = ops.linear_rows(gc, a1["w_ctx"], bias=a1["b"])                    # [B, 128]
+            # the context's share of every column: its utterance's row (a gap column takes some row; nothing reads it)
+            res = ctx.index_select(0, levels.columns).t().contiguous().unsqueeze(0)         # [1, 128, T_tot_3]
+            a = ops.conv1d(x, a1["w"], a1["cout"], 1, res=res, relu=True, relu_first=True, ch_scale=a1["scale"], ch_shift=a1["shift"], mode=W["mode1"])
+            logits = ops.conv1d(ops.tanh_(a), a2["w"], a2["cout"], 1, bias=a2["b"], mode=W["mode1"])
+            pooled = ops.attentive_stats_segments(x, logits, tab)                  # [B, 5120]
+            # A NaN or an infinity among an utterance's samples makes its whole feature segment NaN (the InstanceNorm's mean), and the
+            # reference's ReLU would carry that to the x-vector.  The conv epilogue's ReLU is max(v, 0), which gives 0 for NaN: the NaNs
+            # would end after the stem.  So the segment's NaN is carried past the body as xvector.Net.embed_segments does:
+            # 0 * (sum of the feature rows' means) is 0 for a finite segment and NaN otherwise, added to the pooled row.
+            pooled = pooled + ops.row_mean_segments(feats, levels[0]).sum(1, keepdim=True) * 0.0
+            e = ops.linear_rows(pooled, W["emb"]["w"], ch_scale=W["emb"]["scale"], ch_shift=W["emb"]["shift"])
+            return ops.l2norm_rows(e)
+
+        def extract_batch(self, wavs):
+            """x-vectors of a RAGGED batch in one launch sequence: `wavs` = a list of 1-D device tensors of any lengths, or
+            (padded [B, n_max], lengths) with anything past each length and `lengths` a list or a CPU tensor -> [B, 256], row i the
+            L2-normalised x-vector of utterance i at its own length (what `forward` gives for it alone, to f32 rounding) — and all NaN for
+            an utterance with a NaN or an infinite sample, as the reference's arithmetic gives it (`forward` returns a finite vector there:
+            its ReLUs drop the NaNs).  The utterances lie side by side on one packed time axis per time resolution (ops.ragged_levels); the
+            tables are built on the host from the lengths and uploaded once; nothing waits for the device.
+            The 2-D convs run in exact f32 whatever `conv2d_precision` says (`last_conv2d_arithmetic` = "f32"): a segment form of the
+            split-f16 kernel (csrc/conv2d16/) is out of scope; the attention's two 1x1 convs follow `precision`.
+            Every utterance needs 1 280 samples (two pooled frames, `embed`'s rule); at most 1024 utterances and 32 * 80 * T_tot_0 * 4 <
+            2^31 bytes per call (10 KB per frame for the largest tensor, several of which are live at once)."""
+            if isinstance(wavs, tuple) and len(wavs) == 2 and isinstance(wavs[0], torch.Tensor) and wavs[0].dim() == 2:
+                padded, lengths = wavs
+                lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+                if len(lengths) != padded.shape[0] or (lengths and max(lengths) > padded.shape[1]):
+                    raise _lib.SatError(f"extract_batch: {len(lengths)} lengths up to {max(lengths, default=0)} for a padded batch {tuple(padded.shape)}")
+                tensors = [padded]
+            else:
+                tensors = list(wavs)
+                if any(not isinstance(w, torch.Tensor) or w.dim() != 1 for w in tensors):
+                    raise _lib.SatError("extract_batch: a list of 1-D tensors, or (padded [B, n_max], lengths)")
+                lengths, padded = [int(w.shape[0]) for w in tensors], None
+            if not lengths:
+                raise _lib.SatError("extract_batch: an empty batch")
+            if any(not w.is_cuda for w in tensors):
+                raise _lib.SatError("x-vector extraction runs on the HIP device only (no CPU fallback)")
+            if len(lengths) > ops.RAGGED_MAX_SEGMENTS:
+                raise _lib.SatError(f"extract_batch: {len(lengths)} utterances in one call, at most {ops.RAGGED_MAX_SEGMENTS}")
+            for i, n in enumerate(lengths):
+                if pooled_frames(1 + n // ops.XV_HOP) < 2:
+                    raise _lib.SatError(f"extract_batch: utterance {i} of {n} samples leaves {pooled_frames(1 + n // ops.XV_HOP)} pooled frame; the global "
+                                        "context's unbiased deviation needs two (1 280 samples)")
+            t_tot = ops.ragged_layout([1 + n // ops.XV_HOP for n in lengths])[2]
+            if PLANES[0] * 80 * t_tot * 4 >= 2 ** 31:
+                raise _lib.SatError(f"extract_batch: {t_tot} frames in one call, a 32-channel image of 2^31 bytes or more: split the batch")
+            device = tensors[0].device
+            W = self._prepare(device)
+            if padded is None:
+                padded = tensors[0].to(torch.float32).unsqueeze(0) if len(tensors) == 1 else \
+                    torch.nn.utils.rnn.pad_sequence([w.to(torch.float32) for w in tensors], batch_first=True)
+            padded = padded.to(torch.float32).contiguous()
+            levels = ops.RaggedLevels(device, n_samples=lengths)
+            if self._mel_ranges is None or self._mel_ranges[0] is not W:
+                self._mel_ranges = (W, ops.mel_filter_ranges(W["fb"]))
+            mel = ops.melspec_logmel_segments(padded, levels[0], W["window"], W["fb"], W["coef"], fb_range=self._mel_ranges[1])
+            return self.embed_segments(ops.instnorm_segments(mel, levels[0], out=mel), levels)
 
         def forward(self, x, target=None, taps=None):
             if target is not None:
