@@ -211,6 +211,12 @@ _PROTOS_RAGGED2D = {
     "sat_row_mean_std_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
 }
 
+# include/satools_hip_ragged2d16.h (csrc/ragged2d16/): a sixth table, bound like the other five
+_PROTOS_RAGGED2D16 = {
+    "sat_conv2d_f16x3_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9
+                                      + [C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -239,6 +245,11 @@ def ragged2d_symbols():
     return sorted(_PROTOS_RAGGED2D)
 
 
+def ragged2d16_symbols():
+    """names declared in include/satools_hip_ragged2d16.h that the library must export"""
+    return sorted(_PROTOS_RAGGED2D16)
+
+
 def library_path():
     """where the in-tree shared library lives (built by sa-toolkit_amd/build.py)"""
     return LIB_PATH
@@ -254,7 +265,7 @@ def lib():
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items())
-                                  + list(_PROTOS_RAGGED2D.items())):
+                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items())):
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -446,6 +446,9 @@ def main(argv=None):
     ap.add_argument("--report", action="store_true", help="also print the two lines of the reference's report step (raw, AS-norm)")
     ap.add_argument("--resnet-conv2d", choices=("f32", "f16x3"), default=None,
                     help="arithmetic of the 2-D convs of the ResNet extractor's blocks (its conv2d_precision); an error for the ECAPA model")
+    ap.add_argument("--resnet-conv2d-ragged", choices=("f32", "f16x3"), default=None,
+                    help="arithmetic of the same convs in the ragged batches of --batch-size above 1 (the ResNet extractor's "
+                         "ragged_conv2d_precision, which --resnet-conv2d does not govern); an error for the ECAPA model")
     ap.add_argument("--batch-size", type=int, default=1, metavar="N",
                     help="utterances per extractor call: above 1 the model (ECAPA-TDNN or ResNet) extracts ragged batches of up to N utterances "
                          "of any lengths; 1 = one per call, the reference's way")
@@ -462,6 +465,10 @@ def main(argv=None):
         if not hasattr(model, "conv2d_precision"):
             ap.error("--resnet-conv2d: the loaded model is not the ResNet extractor (it has no 2-D convs)")
         model.conv2d_precision = a.resnet_conv2d
+    if a.resnet_conv2d_ragged is not None:
+        if not hasattr(model, "ragged_conv2d_precision"):
+            ap.error("--resnet-conv2d-ragged: the loaded model is not the ResNet extractor (it has no 2-D convs)")
+        model.ragged_conv2d_precision = a.resnet_conv2d_ragged
     ci = dict(m=a.eer_ci, ci=0.95, seed=a.eer_ci_seed) if a.eer_ci else None
     m = test_metrics(model, a.enrolls_wav_scp, a.trails_wav_scp, a.enroll_utt2spk, a.trials, a.decode_output, as_norm=not a.no_as_norm, eer_ci=ci,
                      **({} if a.batch_size == 1 else dict(batch_size=a.batch_size, max_frames=a.max_frames)))

@@ -1228,3 +1228,37 @@ def row_mean_std_segments(x, tab):
     check(lib().sat_row_mean_std_segments_f32(ptr(x), ptr(out), ptr(tab.seg_off), ptr(tab.seg_len), c, tab.B, tab.T_tot, stream()),
           "sat_row_mean_std_segments_f32")
     return out
+
+
+# ---- split-f16 2-D convs in ragged batches (csrc/ragged2d16/, include/satools_hip_ragged2d16.h) ------------------------------------
+def conv2d_f16x3_segments(x, w_split, descale, ksize, stride, tab_in, tab_out, ch_scale=None, ch_shift=None, relu=False, overflow=None, out=None):
+    """ops.conv2d_f16x3 with every segment of the packed image x [1, Cin, H, T_in] an utterance of its own -> [1, Cout, Ho, T_out], the
+    tables as for ops.conv2d_segments: segment i of the result has the bits of ops.conv2d_f16x3 on utterance i alone.  (w_split, descale)
+    from pack_conv2d_weight_f16x3.  `overflow`: an int32 tensor of tab_in.B elements on x's device, or None; the kernel makes element i
+    nonzero if a staged activation of segment i had |x| >= 65 520 or was not finite (that segment's results are then unspecified), and
+    never clears one.  Gap columns of x raise no flag and reach no result; gap columns of the result are not written."""
+    cin, H, x = _packed3(x, tab_in, "conv2d_f16x3_segments")
+    if w_split.dim() != 6 or w_split.dtype != torch.float16 or not w_split.is_contiguous():
+        raise _lib.SatError("conv2d_f16x3_segments: split weights f16 [Cin / 16, k * k, 2, 2, Cout, 8] (pack_conv2d_weight_f16x3) are needed")
+    chunks, taps, parts, halves, cout, eight = w_split.shape
+    stride = int(stride)
+    if taps != ksize * ksize or chunks * 16 != cin or (parts, halves, eight) != (2, 2, 8) or stride < 1:
+        raise _lib.SatError(f"conv2d_f16x3_segments: split weights {tuple(w_split.shape)} do not fit x {tuple(x.shape)} with ksize {ksize}, stride {stride}")
+    for t in (ch_scale, ch_shift):
+        if t is not None and (t.numel() != cout or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.SatError("conv2d_f16x3_segments: ch_scale / ch_shift are contiguous f32 vectors of Cout values")
+    descale = float(descale)
+    if not (0.0 < descale < float("inf")):
+        raise _lib.SatError(f"conv2d_f16x3_segments: descale = {descale} (the 2^-e pack_conv2d_weight_f16x3 returned)")
+    if tab_out.B != tab_in.B or [(n - 1) // stride + 1 for n in tab_in.frames] != tab_out.frames:
+        raise _lib.SatError(f"conv2d_f16x3_segments: the output table's segments are not the input's at stride {stride}")
+    if overflow is not None and (overflow.dtype != torch.int32 or overflow.numel() != tab_in.B or overflow.device != x.device or not overflow.is_contiguous()):
+        raise _lib.SatError(f"conv2d_f16x3_segments: overflow is {tab_in.B} contiguous int32 (one per segment) on x's device")
+    Ho = (H - 1) // stride + 1
+    y = torch.empty(1, cout, Ho, tab_out.T_tot, dtype=torch.float32, device=x.device) if out is None else out
+    if tuple(y.shape[-3:]) != (cout, Ho, tab_out.T_tot) or y.numel() != cout * Ho * tab_out.T_tot or y.dtype != torch.float32:
+        raise _lib.SatError(f"conv2d_f16x3_segments: out {tuple(y.shape)} is not [1, {cout}, {Ho}, {tab_out.T_tot}]")
+    check(lib().sat_conv2d_f16x3_segments_f32(ptr(x), ptr(w_split), descale, ptr(y), ptr(ch_scale), ptr(ch_shift), int(bool(relu)), ptr(tab_in.seg_off),
+                                              ptr(tab_in.seg_len), ptr(tab_out.seg_off), tab_in.B, max(tab_in.frames), cin, cout, H, tab_in.T_tot,
+                                              tab_out.T_tot, int(ksize), stride, ptr(overflow), stream()), "sat_conv2d_f16x3_segments_f32")
+    return y

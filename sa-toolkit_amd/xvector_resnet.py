@@ -15,6 +15,8 @@ L2-normalised 256-dim embedding — computed on the HIP kernels:
   head        Linear(5120 -> 256) + BatchNorm, L2 norm                                  linear_rows_kernel, l2norm_rows_kernel
   ragged      `extract_batch`: utterances of unequal length side by side on one       csrc/ragged2d/resnet_ragged.hip, the segment forms of
               packed time axis per time resolution, exact f32                          the conv, the squeeze, the tail and the context
+              opt-in (`ragged_conv2d_precision = "f16x3"`): the 36 block convs in         csrc/ragged2d16/  conv2d_segments_f16x3_kernel
+              split-f16 arithmetic, exact f32 again for the utterances that leave the f16 range
 
 AXES.  The reference runs the ResNet on [B, 1, T, 80] images, frequency innermost (sidekit/archi.py:110-113), and permutes its
 [B, 256, T', 10] output to [B, 2560, T'] for the pooling (sidekit/pooling.py:126-128).  Here TIME stays innermost from the front end's
@@ -100,8 +102,14 @@ def build(args=None):
         #: (|x| >= 65 520 or non-finite) is run again in "f32": `split_fallbacks` counts those, `last_conv2d_arithmetic` names what the
         #: last batch's result came from
         conv2d_precision = os.environ.get("SATOOLS_AMD_RESNET_CONV2D", "f32")
+        #: arithmetic of the same convs in a RAGGED call (`extract_batch`), which `conv2d_precision` does not govern: "f32" (the default) or
+        #: "f16x3" (split-f16 on the packed time axis, csrc/ragged2d16/).  An utterance with an activation outside the f16 range is extracted
+        #: again in "f32", alone among its batch: `last_split_fallback_rows` names those of the last ragged call, `split_fallbacks` counts
+        #: the calls that had any, `last_conv2d_arithmetic` is then "f16x3+f32" ("f32" if every row fell back)
+        ragged_conv2d_precision = os.environ.get("SATOOLS_AMD_RESNET_CONV2D_RAGGED", "f32")
         split_fallbacks = 0
         last_conv2d_arithmetic = None
+        last_split_fallback_rows = None
 
         def __init__(self, num_speakers=1):
             super().__init__()
@@ -124,7 +132,9 @@ def build(args=None):
         def _prepare(self, device):
             if self.conv2d_precision not in ("f32", "f16x3"):
                 raise _lib.SatError(f"conv2d_precision = {self.conv2d_precision!r}: \"f32\" or \"f16x3\"")
-            key = (self.precision, self.conv2d_precision) + tuple((p.data_ptr(), p._version, str(p.device)) for p in list(self.parameters()) + list(self.buffers()))
+            if self.ragged_conv2d_precision not in ("f32", "f16x3"):
+                raise _lib.SatError(f"ragged_conv2d_precision = {self.ragged_conv2d_precision!r}: \"f32\" or \"f16x3\"")
+            key = (self.precision, self.conv2d_precision, self.ragged_conv2d_precision) + tuple((p.data_ptr(), p._version, str(p.device)) for p in list(self.parameters()) + list(self.buffers()))
             if self._cache_key == key:
                 return self._cache
             _lib.cache_rebuild_begin(device, self._cache is not None)
@@ -137,18 +147,19 @@ def build(args=None):
                 return s.contiguous(), (f32(bn.bias) - f32(bn.running_mean) * s).contiguous()
 
             split2d = self.conv2d_precision == "f16x3"
+            ragged16 = self.ragged_conv2d_precision == "f16x3"
 
             def cb(conv, bn, stem=False):
                 # the kernel axes swapped: this net keeps time innermost, the reference frequency (module docstring)
                 sc, sh = bn_affine(bn)
                 e = {"w": ops.pack_conv2d_weight(f32(conv.weight), transpose=True), "k": conv.kernel_size[0], "s": conv.stride[0], "scale": sc, "shift": sh}
-                if split2d and not stem:
-                    # (the exact-f32 packing stays: a batch that leaves the f16 range runs on it)
+                if (split2d or ragged16) and not stem:
+                    # (the exact-f32 packing stays: a batch or an utterance that leaves the f16 range runs on it)
                     e["w16"], e["descale"] = ops.pack_conv2d_weight_f16x3(f32(conv.weight), transpose=True)
                 return e
 
             sn = self.sequence_network
-            W = {"stem": cb(sn.conv1, sn.bn1, stem=True), "blocks": [], "split2d": split2d}
+            W = {"stem": cb(sn.conv1, sn.bn1, stem=True), "blocks": [], "split2d": split2d, "ragged16": ragged16}
             for i in range(4):
                 for blk in getattr(sn, f"layer{i + 1}"):
                     W["blocks"].append({"c1": cb(blk.conv1, blk.bn1), "c2": cb(blk.conv2, blk.bn2),
@@ -252,30 +263,40 @@ def build(args=None):
 
         # ---- ragged batches (csrc/ragged2d/, include/satools_hip_ragged2d.h) ------------------------------
         @staticmethod
-        def _conv_segments(x, e, tab_in, tab_out, relu=False):
+        def _conv_segments(x, e, tab_in, tab_out, relu=False, flags=None):
+            """`flags` (the call's int32 overflow flags, one per utterance) selects the split-f16 form"""
+            if flags is not None:
+                return ops.conv2d_f16x3_segments(x, e["w16"], e["descale"], e["k"], e["s"], tab_in, tab_out, ch_scale=e["scale"], ch_shift=e["shift"],
+                                                 relu=relu, overflow=flags)
             return ops.conv2d_segments(x, e["w"], e["k"], e["s"], tab_in, tab_out, ch_scale=e["scale"], ch_shift=e["shift"], relu=relu)
 
-        def _block_segments(self, x, blk, tab_in, tab_out):
+        def _block_segments(self, x, blk, tab_in, tab_out, flags=None):
             """`_block` on the packed images: conv1 and the shortcut go from the input's level to the output's (the same one at stride 1),
             conv2, the squeeze and the tail stay on the output's; the SE layer's two Linear layers see [B, C] rows as in `_block`"""
-            out = self._conv_segments(self._conv_segments(x, blk["c1"], tab_in, tab_out, relu=True), blk["c2"], tab_out, tab_out)
+            out = self._conv_segments(self._conv_segments(x, blk["c1"], tab_in, tab_out, relu=True, flags=flags), blk["c2"], tab_out, tab_out, flags=flags)
             m = ops.plane_mean_segments(out, tab_out)                               # [B, C]
             g = ops.linear_rows(ops.linear_rows(m, blk["fc0"], relu=True), blk["fc2"])
-            r = x if blk["sc"] is None else self._conv_segments(x, blk["sc"], tab_in, tab_out)
+            r = x if blk["sc"] is None else self._conv_segments(x, blk["sc"], tab_in, tab_out, flags=flags)
             return ops.se_scale_add_relu_segments(out, g, r, tab_out)
 
-        def embed_segments(self, feats, levels):
+        def embed_segments(self, feats, levels, overflow=None):
             """`embed` of a packed feature tensor [1, 80, T_tot_0] -> [B, 256]; `levels` = the batch's ops.RaggedLevels.  The 2-D convs
-            run in exact f32 (csrc/ragged2d/; there is no segment form of the split-f16 kernel).  Gap columns of every intermediate hold
-            anything: the segment kernels never read them, and the attention's 1x1 convs are pointwise in time."""
+            run in exact f32 (csrc/ragged2d/) unless `overflow` is given: an int32 tensor of B elements on the device, zeroed by the
+            caller, with which the 36 block convs run in split-f16 arithmetic (csrc/ragged2d16/; `ragged_conv2d_precision` must be
+            "f16x3", which packs their weights).  Element i is nonzero afterwards if an activation of utterance i left the f16 range: row i
+            is then unspecified and the caller replaces it (`extract_batch` does); every other row is unaffected.  The stem is exact f32
+            either way.  Gap columns of every intermediate hold anything: the segment kernels never read them, and the attention's 1x1
+            convs are pointwise in time."""
             W = self._prepare(feats.device)
-            self.last_conv2d_arithmetic = "f32"
+            if overflow is not None and not W["ragged16"]:
+                raise _lib.SatError("embed_segments: overflow flags select the split-f16 convs, which need ragged_conv2d_precision = \"f16x3\"")
+            self.last_conv2d_arithmetic = "f32" if overflow is None else "f16x3"
             x = self._conv_segments(feats.view(1, 1, feats.shape[-2], feats.shape[-1]), W["stem"], levels[0], levels[0], relu=True)
             i, lvl = 0, 0
             for li, n in enumerate(BLOCKS):
                 for j in range(n):
                     nxt = lvl + 1 if (li > 0 and j == 0) else lvl
-                    x = self._block_segments(x, W["blocks"][i], levels[lvl], levels[nxt])
+                    x = self._block_segments(x, W["blocks"][i], levels[lvl], levels[nxt], overflow)
                     i, lvl = i + 1, nxt
             tab = levels[lvl]
             x = x.view(1, x.shape[1] * x.shape[2], x.shape[3])                     # [1, 2560, T_tot_3]
@@ -302,8 +323,14 @@ def build(args=None):
             an utterance with a NaN or an infinite sample, as the reference's arithmetic gives it (`forward` returns a finite vector there:
             its ReLUs drop the NaNs).  The utterances lie side by side on one packed time axis per time resolution (ops.ragged_levels); the
             tables are built on the host from the lengths and uploaded once; nothing waits for the device.
-            The 2-D convs run in exact f32 whatever `conv2d_precision` says (`last_conv2d_arithmetic` = "f32"): a segment form of the
-            split-f16 kernel (csrc/conv2d16/) is out of scope; the attention's two 1x1 convs follow `precision`.
+            The 2-D convs run in exact f32 whatever `conv2d_precision` says (`last_conv2d_arithmetic` = "f32") unless
+            `ragged_conv2d_precision` is "f16x3": the 36 block convs then run in split-f16 arithmetic (csrc/ragged2d16/, the segment form
+            of the csrc/conv2d16/ kernel) with one overflow flag per utterance, read once after the call's last launch.  Unflagged
+            utterances keep their rows; the flagged ones are extracted again as one ragged sub-batch in exact f32 and their rows
+            scattered in, so that every row is what `forward` gives for that utterance alone under `conv2d_precision` = "f16x3", its own
+            fallback included.  `last_split_fallback_rows` holds their sorted indices ([] without any), `split_fallbacks` rises by one for
+            a call with any, and `last_conv2d_arithmetic` is "f16x3", "f16x3+f32" or, when every row fell back, "f32".  The attention's
+            two 1x1 convs follow `precision`.
             Every utterance needs 1 280 samples (two pooled frames, `embed`'s rule); at most 1024 utterances and 32 * 80 * T_tot_0 * 4 <
             2^31 bytes per call (10 KB per frame for the largest tensor, several of which are live at once)."""
             if isinstance(wavs, tuple) and len(wavs) == 2 and isinstance(wavs[0], torch.Tensor) and wavs[0].dim() == 2:
@@ -336,11 +363,29 @@ def build(args=None):
                 padded = tensors[0].to(torch.float32).unsqueeze(0) if len(tensors) == 1 else \
                     torch.nn.utils.rnn.pad_sequence([w.to(torch.float32) for w in tensors], batch_first=True)
             padded = padded.to(torch.float32).contiguous()
-            levels = ops.RaggedLevels(device, n_samples=lengths)
+            if not W["ragged16"]:
+                self.last_split_fallback_rows = []
+                return self._extract_packed(W, padded, lengths, None)
+            # one zeroed flag per utterance (the call's own allocation), read once after everything is launched
+            flags = torch.zeros(len(lengths), dtype=torch.int32, device=device)
+            rows = self._extract_packed(W, padded, lengths, flags)
+            bad = torch.nonzero(flags).flatten().tolist()
+            self.last_split_fallback_rows = bad
+            if bad:
+                # these utterances left the f16 range: exact f32 for them, as one ragged sub-batch of their own
+                self.split_fallbacks += 1
+                idx = torch.tensor(bad, dtype=torch.long, device=device)
+                rows[idx] = self._extract_packed(W, padded.index_select(0, idx), [lengths[i] for i in bad], None)
+                self.last_conv2d_arithmetic = "f32" if len(bad) == len(lengths) else "f16x3+f32"
+            return rows
+
+        def _extract_packed(self, W, padded, lengths, overflow):
+            """padded [B, n_max] f32 on the device and the host's lengths -> [B, 256]: the tables, the front end and `embed_segments`"""
+            levels = ops.RaggedLevels(padded.device, n_samples=lengths)
             if self._mel_ranges is None or self._mel_ranges[0] is not W:
                 self._mel_ranges = (W, ops.mel_filter_ranges(W["fb"]))
             mel = ops.melspec_logmel_segments(padded, levels[0], W["window"], W["fb"], W["coef"], fb_range=self._mel_ranges[1])
-            return self.embed_segments(ops.instnorm_segments(mel, levels[0], out=mel), levels)
+            return self.embed_segments(ops.instnorm_segments(mel, levels[0], out=mel), levels, overflow)
 
         def forward(self, x, target=None, taps=None):
             if target is not None:
