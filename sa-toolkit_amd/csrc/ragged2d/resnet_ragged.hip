@@ -1,50 +1,18 @@
 // Segment forms of the ResNet x-vector extractor's kernels (csrc/conv2d.hip) for a RAGGED batch on a packed time axis
 // (include/satools_hip_ragged2d.h: B utterances of unequal length side by side in one image [C][H][T_tot], time innermost, segment i at
-// columns off_i .. off_i + T_i - 1 of every row, gap columns between them that hold anything; one table per time resolution).  Each kernel
-// keeps the order of operations of the kernel it comes from, so that segment i of its result has the bits of that kernel's result on
-// utterance i alone; each selects on load (a gap column or another segment never reaches an output, NaN included) and skips what a wrong
-// table names.  csrc/conv2d.hip itself is untouched: the conv's K loop is restated here (as csrc/ragged/ restates its row kernels).
-#include "../common.h"
+// columns off_i .. off_i + T_i - 1 of every row, gap columns between them that hold anything; one table per time resolution).  The convs and
+// the pooling run the per-call kernels' own bodies (csrc/conv2d_tile.h) on each segment, the other two keep the order of operations of the
+// kernel they come from, so that segment i of a result has the bits of the per-call kernel's result on utterance i alone; each selects on
+// load (a gap column or another segment never reaches an output, NaN included) and skips what a wrong table names (segments.h).
+#include "../conv2d_tile.h"
+#include "segments.h"
 #include "../../../include/satools_hip_ragged2d.h"
 
 namespace sat {
 
-typedef float r2_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int R2_TH = 4;     // output rows per block: one per wave              (C2_TH of csrc/conv2d.hip)
-constexpr int R2_TW = 32;    // output columns per block, in the segment's own coordinates: the N of one 32x32 MFMA tile   (C2_TW)
-constexpr int R2_CI = 8;     // input channels per staged chunk                     (C2_CI)
-constexpr int R2_STEM_CO = 32;
-
-__device__ __forceinline__ float r2_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// segment i of one table -> (first column, columns); false for an entry that does not lie inside 0 .. T - 1
-__device__ __forceinline__ bool r2_segment(const int* __restrict__ seg_off, const int* __restrict__ seg_len, int i, int T, int* off, int* len) {
-  const int o = seg_off[i], l = seg_len[i];
-  *off = o;
-  *len = l;
-  return o >= 0 && l >= 1 && o < T && l <= T - o;
-}
-
-// segment i of a conv: W input columns from column `in` of x's rows, Wo = (W - 1) / S + 1 output columns from column `out` of y's rows;
-// false unless both lie inside their rows and W <= max_len (the bound the grid was sized by: a longer segment would be computed in part)
-__device__ __forceinline__ bool r2_conv_segment(const int* __restrict__ in_off, const int* __restrict__ in_len, const int* __restrict__ out_off, int i,
-                                                int T_in, int T_out, int max_len, int S, int* in, int* W, int* out, int* Wo) {
-  if (!r2_segment(in_off, in_len, i, T_in, in, W) || *W > max_len) return false;
-  const int o = out_off[i], wo = (*W - 1) / S + 1;
-  *out = o;
-  *Wo = wo;
-  return o >= 0 && o < T_out && wo <= T_out - o;
-}
-
-// conv2d_mfma_kernel (csrc/conv2d.hip) with a block per (segment, 32 MT output channels, R2_TH x R2_TW output pixels of the segment): the
-// image's width is the segment's W, on the loads (columns outside 0 .. W - 1 read as zero: the padding at the utterance's own ends, whatever
-// the gap or the neighbour holds) and on the stores alike; rows are T_in / T_out apart.  The chunk order, the tap order, the channel pairs and
-// the register-staged prefetch are that kernel's, so every accumulator sees the same MFMAs on the same values in the same order.
+// the MFMA conv's tile body (csrc/conv2d_tile.h) with a block per (segment, 32 MT output channels, C2_TH x C2_TW output pixels of the segment): the image's width is the
+// segment's W, on the loads (the padding at the utterance's own ends, whatever the gap or the neighbour holds) and on the stores alike;
+// rows are T_in / T_out apart.
 // The grid's x extent comes from max_len; a block past its segment's last tile leaves before the first barrier (block-uniform).
 template <int KS, int S, int MT>
 __global__ void __launch_bounds__(256) conv2d_segments_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y,
@@ -52,134 +20,31 @@ __global__ void __launch_bounds__(256) conv2d_segments_mfma_kernel(const float* 
                                                                    const int* __restrict__ in_off, const int* __restrict__ in_len,
                                                                    const int* __restrict__ out_off, int Cin, int Cout, int H, int T_in, int Ho,
                                                                    int T_out, int max_len, int row_tiles, int relu) {
-  constexpr int P = KS / 2;
-  constexpr int R = S * (R2_TH - 1) + KS;
-  constexpr int WC = S * (R2_TW - 1) + KS;
-  constexpr int WP = WC | 1;
-  constexpr int PL = R * WP + ((R * WP) % 2 == 0 ? 1 : 0);
-  constexpr int COT = 32 * MT;
-  constexpr int TAPS = KS * KS;
-  __shared__ float xs[R2_CI * PL];
-  __shared__ float wl[TAPS * R2_CI * COT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   int in, W, out, Wo;
-  if (!r2_conv_segment(in_off, in_len, out_off, blockIdx.z, T_in, T_out, max_len, S, &in, &W, &out, &Wo)) return;
-  const int wo0 = blockIdx.x * R2_TW;
+  if (!ragged_conv_segment(in_off, in_len, out_off, blockIdx.z, T_in, T_out, max_len, S, &in, &W, &out, &Wo)) return;
+  const int wo0 = blockIdx.x * C2_TW;
   if (wo0 >= Wo) return;
   const int rt = blockIdx.y % row_tiles, ct = blockIdx.y / row_tiles;
-  const int ho0 = rt * R2_TH, co0 = ct * COT;
-  const int gh0 = S * ho0 - P, gw0 = S * wo0 - P;
+  const int ho0 = rt * C2_TH, co0 = ct * (32 * MT);
+  const int xpitch = T_in, ypitch = T_out;
   const float* xb = x + in;
-
-  r2_f32x16 acc[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-
-  constexpr int NXE = R2_CI * R * WC, NX = (NXE + 255) / 256;
-  constexpr int NW = TAPS * R2_CI * COT / 256;
-  static_assert(TAPS * R2_CI * COT % 256 == 0, "a whole number of weight elements per thread");
-  float xr[NX], wr[NW];
-  const auto fetch = [&](int ci0) {
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const int i = tid + 256 * k;
-      const int ci = i / (R * WC), rem = i - ci * (R * WC), r = rem / WC, c = rem - r * WC;
-      const int gh = gh0 + r, gw = gw0 + c;
-      float v = 0.f;
-      if (i < NXE && gh >= 0 && gh < H && gw >= 0 && gw < W) v = xb[((size_t)(ci0 + ci) * H + gh) * T_in + gw];
-      xr[k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      const int i = tid + 256 * k;
-      const int tap = i / (R2_CI * COT), rem = i - tap * (R2_CI * COT), ci = rem / COT, co = rem - ci * COT;
-      wr[k] = w[((size_t)tap * Cin + ci0 + ci) * Cout + co0 + co];
-    }
-  };
-  fetch(0);
-  for (int ci0 = 0; ci0 < Cin; ci0 += R2_CI) {
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const int i = tid + 256 * k;
-      const int ci = i / (R * WC), rem = i - ci * (R * WC), r = rem / WC, c = rem - r * WC;
-      if (i < NXE) xs[ci * PL + r * WP + c] = xr[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NW; ++k) wl[tid + 256 * k] = wr[k];
-    __syncthreads();
-    if (ci0 + R2_CI < Cin) fetch(ci0 + R2_CI);
-    const float* xa = xs + lh * PL + (S * wave) * WP + S * l31;
-    const float* wa = wl + lh * COT + l31;
-#pragma unroll
-    for (int kh = 0; kh < KS; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-        for (int kk = 0; kk < R2_CI / 2; ++kk) {
-          const float bv = xa[2 * kk * PL + kh * WP + kw];
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const float av = wa[((kh * KS + kw) * R2_CI + 2 * kk) * COT + 32 * m];
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[m], 0, 0, 0);
-          }
-        }
-    __syncthreads();
-  }
-
-  const int ho = ho0 + wave, wo = wo0 + l31;
-  if (ho >= Ho || wo >= Wo) return;
-  float* yb = y + (size_t)ho * T_out + out + wo;
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      float v = acc[m][r];
-      if (scale) v = v * scale[co] + shift[co];
-      if (relu) v = fmaxf(v, 0.f);
-      yb[(size_t)co * Ho * T_out] = v;
-    }
+  float* yb = y + out;
+#include "../conv2d_tile_body.h"
 }
 
-// conv2d_stem_kernel per segment: one thread per output pixel of the segment, the same fmaf chain over the nine taps
+// the stem body (csrc/conv2d_tile.h) per segment: one thread per output pixel of the segment
 __global__ void __launch_bounds__(256) conv2d_segments_stem_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y,
                                                                    const float* __restrict__ scale, const float* __restrict__ shift,
                                                                    const int* __restrict__ in_off, const int* __restrict__ in_len,
                                                                    const int* __restrict__ out_off, int H, int T_in, int T_out, int max_len,
                                                                    int relu) {
-  __shared__ float ws[9 * R2_STEM_CO], s_sc[R2_STEM_CO], s_sh[R2_STEM_CO];
   int in, W, out, Wo;
   // (block-uniform: nothing below is reached by a part of the block)
-  if (!r2_conv_segment(in_off, in_len, out_off, blockIdx.z, T_in, T_out, max_len, 1, &in, &W, &out, &Wo) || (int)blockIdx.x * 256 >= W) return;
-  for (int i = threadIdx.x; i < 9 * R2_STEM_CO; i += 256) ws[i] = w[i];
-  if (threadIdx.x < R2_STEM_CO) {
-    s_sc[threadIdx.x] = scale ? scale[threadIdx.x] : 1.f;
-    s_sh[threadIdx.x] = scale ? shift[threadIdx.x] : 0.f;
-  }
-  __syncthreads();
-  const int wo = blockIdx.x * 256 + threadIdx.x, ho = blockIdx.y;
-  if (wo >= W) return;
+  if (!ragged_conv_segment(in_off, in_len, out_off, blockIdx.z, T_in, T_out, max_len, 1, &in, &W, &out, &Wo) || (int)blockIdx.x * 256 >= W) return;
+  const int xpitch = T_in, ypitch = T_out;
   const float* xb = x + in;
-  float v9[9];
-#pragma unroll
-  for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-      const int gh = ho - 1 + kh, gw = wo - 1 + kw;
-      v9[kh * 3 + kw] = (gh >= 0 && gh < H && gw >= 0 && gw < W) ? xb[(size_t)gh * T_in + gw] : 0.f;
-    }
-  float* yb = y + (size_t)ho * T_out + out + wo;
-#pragma unroll 4
-  for (int co = 0; co < R2_STEM_CO; ++co) {
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) v = __builtin_fmaf(ws[t * R2_STEM_CO + co], v9[t], v);
-    if (scale) v = v * s_sc[co] + s_sh[co];
-    if (relu) v = fmaxf(v, 0.f);
-    yb[(size_t)co * H * T_out] = v;
-  }
+  float* yb = y + out;
+#include "../conv2d_stem_body.h"
 }
 
 // row_mean_rows_kernel (csrc/xvector.hip) on the utterance's own contiguous [H][T] plane: element n = h T + t goes to lane n % 64 in turn
@@ -192,7 +57,7 @@ __global__ void __launch_bounds__(256) plane_mean_segments_kernel(const float* _
   if (wv >= C * B) return;
   const int c = wv / B, i = wv - c * B;
   int off, T;
-  if (!r2_segment(seg_off, seg_len, i, T_tot, &off, &T)) return;
+  if (!ragged_segment(seg_off, seg_len, i, T_tot, &off, &T)) return;
   const float* xc = x + (size_t)c * H * T_tot + off;
   const int q = 64 / T, r = 64 - q * T;
   const long long N = (long long)H * T;
@@ -207,7 +72,7 @@ __global__ void __launch_bounds__(256) plane_mean_segments_kernel(const float* _
       ++h;
     }
   }
-  s = r2_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) y[(size_t)i * C + c] = s / (float)N;
 }
 
@@ -219,7 +84,7 @@ __global__ void __launch_bounds__(256) se_scale_add_relu_segments_kernel(const f
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int ch = blockIdx.y, seg = blockIdx.z;
   int off, T;
-  if (!r2_segment(seg_off, seg_len, seg, T_tot, &off, &T) || T > max_len || t >= T) return;
+  if (!ragged_segment(seg_off, seg_len, seg, T_tot, &off, &T) || T > max_len || t >= T) return;
   const float gate = 1.0f / (1.0f + expf(-g[(size_t)seg * C + ch]));
   size_t i = (size_t)ch * H * T_tot + off + t;
   for (int h = 0; h < H; ++h, i += T_tot) {
@@ -228,7 +93,7 @@ __global__ void __launch_bounds__(256) se_scale_add_relu_segments_kernel(const f
   }
 }
 
-// row_mean_std_kernel per (row, segment): x [R][T_tot] -> out [B][2R], means then unbiased deviations.  One wave each; T < 2 is skipped
+// row_mean_std_kernel per (row, segment), on the same row_mean_sqdev_wave: x [R][T_tot] -> out [B][2R], means then unbiased deviations.  One wave each; T < 2 is skipped
 __global__ void __launch_bounds__(256) row_mean_std_segments_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                     const int* __restrict__ seg_off, const int* __restrict__ seg_len, int R, int B,
                                                                     int T_tot) {
@@ -237,17 +102,9 @@ __global__ void __launch_bounds__(256) row_mean_std_segments_kernel(const float*
   if (wv >= R * B) return;
   const int c = wv / B, b = wv - c * B;
   int off, T;
-  if (!r2_segment(seg_off, seg_len, b, T_tot, &off, &T) || T < 2) return;
-  const float* xr = x + (size_t)c * T_tot + off;
-  float s = 0.f;
-  for (int t = lane; t < T; t += 64) s += xr[t];
-  const float mean = r2_wave_sum(s) / (float)T;
-  float q = 0.f;
-  for (int t = lane; t < T; t += 64) {
-    const float d = xr[t] - mean;
-    q = __builtin_fmaf(d, d, q);
-  }
-  q = r2_wave_sum(q);
+  if (!ragged_segment(seg_off, seg_len, b, T_tot, &off, &T) || T < 2) return;
+  float mean, q;
+  row_mean_sqdev_wave(x + (size_t)c * T_tot + off, T, lane, &mean, &q);
   if (lane == 0) {
     out[(size_t)b * 2 * R + c] = mean;
     out[(size_t)b * 2 * R + R + c] = sqrtf(q / (float)(T - 1));
@@ -258,8 +115,8 @@ template <int KS, int S, int MT>
 static int launch_conv2d_segments(const float* x, const float* w, float* y, const float* scale, const float* shift, const int32_t* in_off,
                                   const int32_t* in_len, const int32_t* out_off, int B, int Cin, int Cout, int H, int T_in, int Ho, int T_out,
                                   int max_len, int relu, hipStream_t stream) {
-  const int row_tiles = ceil_div(Ho, R2_TH);
-  const dim3 grid(ceil_div((max_len - 1) / S + 1, R2_TW), row_tiles * (Cout / (32 * MT)), B);
+  const int row_tiles = ceil_div(Ho, C2_TH);
+  const dim3 grid(ceil_div((max_len - 1) / S + 1, C2_TW), row_tiles * (Cout / (32 * MT)), B);
   hipLaunchKernelGGL((conv2d_segments_mfma_kernel<KS, S, MT>), grid, dim3(256), 0, stream, x, w, y, scale, shift, in_off, in_len, out_off, Cin,
                      Cout, H, T_in, Ho, T_out, max_len, row_tiles, relu);
   SAT_LAUNCH_CHECK("conv2d_segments_mfma_kernel");
@@ -287,7 +144,7 @@ extern "C" int sat_conv2d_segments_f32(const float* x, const float* w_packed, fl
   SAT_REQUIRE((long long)Cin * H * T_in < (1ll << 31) && (long long)Cout * Ho * T_out < (1ll << 31), "conv2d_segments: an image exceeds 2^31 elements");
   hipStream_t st = (hipStream_t)stream;
   if (Cin == 1) {
-    SAT_REQUIRE(Cout == R2_STEM_CO && ksize == 3 && stride == 1,
+    SAT_REQUIRE(Cout == C2_STEM_CO && ksize == 3 && stride == 1,
                 "conv2d_segments: Cin = 1 is the stem only (Cout = 32, 3x3, stride 1), got Cout = %d, ksize %d, stride %d", Cout, ksize, stride);
     SAT_REQUIRE(H <= 65535, "conv2d_segments: H = %d exceeds the grid", H);
     hipLaunchKernelGGL(conv2d_segments_stem_kernel, dim3(ceil_div(max_len, 256), H, B), dim3(256), 0, st, x, w_packed, y, ch_scale, ch_shift, in_off,
@@ -298,7 +155,7 @@ extern "C" int sat_conv2d_segments_f32(const float* x, const float* w_packed, fl
   const auto ok = [](int c) { return c == 32 || c == 64 || c == 128 || c == 256; };
   SAT_REQUIRE(ok(Cin) && ok(Cout), "conv2d_segments: Cin = %d / Cout = %d (32, 64, 128 or 256; Cin = 1 for the stem)", Cin, Cout);
   const int mt = Cout == 32 ? 1 : 2;
-  SAT_REQUIRE((long long)ceil_div(Ho, R2_TH) * (Cout / (32 * mt)) <= 65535, "conv2d_segments: H = %d exceeds the grid", H);
+  SAT_REQUIRE((long long)ceil_div(Ho, C2_TH) * (Cout / (32 * mt)) <= 65535, "conv2d_segments: H = %d exceeds the grid", H);
 #define SAT_R2(KS_, S_)                                                                                                                              \
   (mt == 1 ? launch_conv2d_segments<KS_, S_, 1>(x, w_packed, y, ch_scale, ch_shift, in_off, in_len, out_off, B, Cin, Cout, H, T_in, Ho, T_out, max_len, relu, st) \
            : launch_conv2d_segments<KS_, S_, 2>(x, w_packed, y, ch_scale, ch_shift, in_off, in_len, out_off, B, Cin, Cout, H, T_in, Ho, T_out, max_len, relu, st))

@@ -192,8 +192,9 @@ def test_the_conv2d16_dispatch_family_list_is_the_one_in_the_sources():
 
 
 def test_the_gpu_tests_shapes_straddle_the_kernels_tiles():
+    tile = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "conv2d16_tile.h")).read()      # the tile body the kernel calls
+    assert int(re.search(r"constexpr int C16_TH = (\d+);", tile).group(1)) == hc.TH == 4
     text = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "conv2d16", "conv2d_f16x3.hip")).read()
-    assert int(re.search(r"constexpr int C16_TH = (\d+);", text).group(1)) == hc.TH
     assert "SAT_C16(3, 1, 2, 2)" in text and "SAT_C16(3, 2, 1, 1)" in text       # 32 NT output columns: 64 at stride 1, 32 at stride 2
     assert {(3, 63), (4, 64), (5, 65)} <= set(hc.SHAPES)                          # below / at / above 4 x 64 at stride 1
     assert {(7, 63), (8, 64), (9, 65)} <= set(hc.SHAPES)                          # outputs 4x32, 4x32, 5x33 at stride 2: 2 TH - 1 .. and 2 TW2 - 1 ..

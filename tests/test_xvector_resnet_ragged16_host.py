@@ -105,9 +105,11 @@ def test_the_ragged2d16_dispatch_family_list_is_the_one_in_the_sources():
 
 
 def test_the_gpu_tests_widths_are_the_ones_the_sources_tile_constants_need():
+    tile = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "conv2d16_tile.h")).read()      # the tile body both forms call
+    th = int(re.search(r"constexpr int C16_TH = (\d+);", tile).group(1))
+    assert re.search(r"constexpr int TWB = 32 \* NT;", tile)
     text = open(SOURCE).read()
-    th = int(re.search(r"constexpr int R16_TH = (\d+);", text).group(1))
-    assert re.search(r"constexpr int TWB = 32 \* NT;", text)
+    assert '#include "../conv2d16_tile.h"' in text and "conv2d_f16x3_tile<KS, S, MT, NT>(" in text
     nt = {(int(k), int(s)): int(n) for k, s, _, n in re.findall(r"SAT_R16\((\d), (\d), (\d), (\d)\)", text)}
     assert nt == {(3, 1): 2, (3, 2): 1, (1, 1): 2, (1, 2): 1}                        # 64 output columns per block at stride 1, 32 at stride 2
     tw1, tw2 = 32 * nt[(3, 1)], 32 * nt[(3, 2)]

@@ -184,8 +184,9 @@ def test_the_ragged2d_dispatch_family_list_is_the_one_in_the_sources():
 
 
 def test_the_gpu_tests_shapes_are_the_ones_the_kernels_edges_need():
-    text = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged2d", "resnet_ragged.hip")).read()
-    th, tw = (int(re.search(rf"constexpr int {n} = (\d+);", text).group(1)) for n in ("R2_TH", "R2_TW"))
+    tile = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "conv2d_tile.h")).read()        # the tile body both forms call
+    th, tw = (int(re.search(rf"constexpr int {n} = (\d+);", tile).group(1)) for n in ("C2_TH", "C2_TW"))
+    assert '#include "../conv2d_tile_body.h"' in open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged2d", "resnet_ragged.hip")).read()
     assert (th, tw) == (4, 32)
     assert sorted(hr.WIDTHS) == [1, 2, tw - 1, tw, tw + 1, 2 * tw - 1, 2 * tw, 2 * tw + 1, 3 * tw + 1] and list(hr.WIDTHS) != sorted(hr.WIDTHS)
     assert {hr.out_widths((w,), 2)[0] for w in (63, 64, 65)} == {tw, tw + 1}
