@@ -489,7 +489,17 @@ int sat_pcm16_from_f32(const float* x, int16_t* y, long long n, void* stream);
  * (torchaudio's _lfilter normalises b and a by a0 first; FIR = fma chain in tap order, see csrc/yaapt.hip).
  *   wav [B][n]  ->  f0 [B][nframes] (Hz, 0 = unvoiced);  status [B] (device int32):
  *   0 ok, 1 = no voiced frame (the reference raises RuntimeError there), 2 = NCCF window
- *   invalid (the reference's assert N > 0).
+ *   invalid (the reference's assert N > 0), 3 = empty lag window, lag_max < lag_min: the spectral
+ *   pitch lies outside f0_min .. f0_max by more than two deviations (the reference fails in
+ *   crs_corr's stride_matrix, a RuntimeError), or, in a ragged batch, an utterance whose own zero
+ *   extension is negative (below).  Of 2 and 3 the code of the FIRST frame that has one is kept:
+ *   the reference walks the frames in order and ends there.  4 = in a ragged batch, an utterance
+ *   whose tda frame count differs from its frame count (refused for the plan's own length; the
+ *   track of such a row is not valid).
+ * Plans outside the supported region are refused before anything is launched (INTEGRATION.md has
+ * the region in one table); among them frame_space > frame_length at a length where
+ * nframe_size + (nframes - 1) * frame_jump < L: the reference fails there on a negative zero
+ * extension of spec_track (yaapt.py:206-210).
  * hann [frame_size], kaiser [2*frame_size], twiddle [4096][2] = exp(-2*pi*i*k/8192) are device
  * tables built by the host.
  * ------------------------------------------------------------------------------------------ */

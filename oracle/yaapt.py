@@ -31,6 +31,10 @@ class Plan:
 
     def __init__(self, n, opts):
         p = dict(DEFAULTS)
+        if "frame_lengtht" in opts:                       # the YAAPT 4.0 spelling of tda_frame_length (yaapt.py:802-810)
+            opts = dict(opts)
+            old = opts.pop("frame_lengtht")
+            opts.setdefault("tda_frame_length", old)
         p.update(opts)
         self.p = p
         self.fs = p["sr"]
@@ -66,6 +70,9 @@ class Plan:
         self.tda_nframes = min(int((self.L - (self.tda_len - self.frame_jump)) / self.frame_jump), self.nframes)
         self.maxcands = int(p["nccf_maxcands"])
         self.nccf_center = math.floor(p["nccf_pwidth"] / 2.0)
+        self.median_value = int(p["median_value"])
+        # samples spec_track reads: its zero extension (yaapt.py:206-210) has need - L samples and fails when that is negative
+        self.need = self.nframe_size + (self.nframes - 1) * self.frame_jump
 
 
 def medfilt(x, k):

@@ -721,6 +721,13 @@ __global__ void __launch_bounds__(64) yaapt_spec_post_kernel(const float* __rest
   const float* cp = cand + (size_t)b * 8 * nfs;
   const float* cm = cp + 4 * (size_t)nfs;
   for (int f = lane; f < nf; f += 64) spec[f] = cp[f];
+  // a shorter utterance of a ragged batch whose last spectral frame ends inside its own padded length: the reference fails on the
+  // negative zero extension (yaapt.py:206-210).  yaapt_run refuses it for the plan's own length; only a kernel sees the others
+  if (U && lane == 0 && P.nframe_size + (nf - 1) * P.frame_jump < U[b * 4 + 1]) atomicMax(&status[b], 3);
+  // ... or whose tda frame count differs from its analysis frame count (yaapt_run refuses that too for the plan's own length: the
+  // NCCF kernel walks the analysis frames and would read frame means that were never written): status 4, a refusal after the fact
+  if (U && lane == 0 && U[b * 4 + 3] != nf) atomicMax(&status[b], 4);
+  if (lane == 0) ((int*)scal)[b * 4 + 1] = 0x7fffffff;   // first frame on which the reference's time_track fails, and how (nccf kernel)
   const int nv = compact_frames(nf, [&](int f) { return cp[f] > 0.f; }, vidx);
   __syncthreads();
   for (int i = lane; i < nv; i += 64) {
@@ -731,7 +738,7 @@ __global__ void __launch_bounds__(64) yaapt_spec_post_kernel(const float* __rest
   float pitch_avg, pitch_std;
   if (nv == 0) {
     // the reference fails here (medfilt of an empty tensor, yaapt.py:257 -> :54-69); report it
-    if (lane == 0) status[b] = 1;
+    if (lane == 0) atomicMax(&status[b], 1);
     pitch_avg = 150.f;
     pitch_std = NAN;
   } else {
@@ -856,7 +863,7 @@ __global__ void __launch_bounds__(256) yaapt_frame_means_kernel(const float* __r
 
 // NCCF candidate of one (utterance, signal, frame)
 __global__ void __launch_bounds__(256) yaapt_nccf_kernel(const float* __restrict__ filt, const float* __restrict__ fmean,
-                                                        const float* __restrict__ spec, const float* __restrict__ scal,
+                                                        const float* __restrict__ spec, float* __restrict__ scal,
                                                         float* __restrict__ tp, float* __restrict__ tm,
                                                         int* __restrict__ status, const int* __restrict__ U, const Plan P) {
   __shared__ float d[1024];
@@ -880,8 +887,14 @@ __global__ void __launch_bounds__(256) yaapt_nccf_kernel(const float* __restrict
     const int lag_min = (int)fa - P.nccf_center;
     const int lag_max = (int)fb + P.nccf_center;
     const int N = n - lag_max;
+    // The reference walks the frames in order and ends at the first that fails: scal[1] keeps the smallest (frame, code), both
+    // signals of a frame have the same lags and so the same code; yaapt_refine_dp_kernel turns it into the utterance's status
     if (N <= 0 || lag_min < 1) {
-      if (tid == 0) status[b] = 2;  // the reference asserts N > 0 (yaapt.py:586)
+      if (tid == 0) atomicMin((int*)scal + b * 4 + 1, k * 4 + 2);  // the reference asserts N > 0 (yaapt.py:586)
+    } else if (lag_max < lag_min) {
+      // the spectral pitch lies outside [f0_min, f0_max] by more than two deviations: the reference asks stride_matrix for
+      // lag_max - lag_min < 0 rows and fails (yaapt.py:594)
+      if (tid == 0) atomicMin((int*)scal + b * 4 + 1, k * 4 + 3);
     } else {
       const float* x = filt + ((size_t)b * 2 + sig) * P.Lz + (size_t)k * P.frame_jump;
       const float* fm = fmean + ((size_t)b * 2 + sig) * nf;
@@ -962,12 +975,17 @@ __global__ void __launch_bounds__(256) yaapt_nccf_kernel(const float* __restrict
 __global__ void __launch_bounds__(64) yaapt_refine_dp_kernel(const float* __restrict__ tp, const float* __restrict__ tm,
                                                             const float* __restrict__ spec, const float* __restrict__ energy,
                                                             const int* __restrict__ vuv, float* __restrict__ f0,
-                                                            const int* __restrict__ U, const Plan P) {
+                                                            const float* __restrict__ scal, int* __restrict__ status,
+                                                            float* __restrict__ refined, const int* __restrict__ U, const Plan P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   const int nfs = P.nframes;                      // row stride in global memory
   const int nf = ulen(U, b, 2, nfs);              // frames of this utterance (also the LDS row pitch)
+  if (lane == 0) {                                // the first frame the NCCF kernel could not do, if any: 2 or 3
+    const int key = ((const int*)scal)[b * 4 + 1];
+    if (key != 0x7fffffff) atomicMax(&status[b], key & 3);
+  }
   float* rp = lds;
   float* rm = rp + NC * (size_t)nf;
   float* ta = rm + NC * (size_t)nf;
@@ -1047,6 +1065,10 @@ __global__ void __launch_bounds__(64) yaapt_refine_dp_kernel(const float* __rest
     else rm[(NC - 2) * nf + k] = 1.0f - tmin(1.f, e / 2.0f);
     rp[(NC - 3) * nf + k] = sp[k];
     rm[(NC - 3) * nf + k] = e / 5.0f;
+    // refine()'s result for the tests (f0.workspace_views: "refined" = pitch[6], merit[6]): nothing else shows most of its branches,
+    // the final track picks one row per frame
+    float* rd = refined + (size_t)b * 2 * NC * nfs;
+    for (int r = 0; r < NC; ++r) { rd[(size_t)r * nfs + k] = rp[r * nf + k]; rd[(size_t)(NC + r) * nfs + k] = rm[r * nf + k]; }
     for (int r = 0; r < NC; ++r) rm[r * nf + k] = 1.f - rm[r * nf + k];   // local cost of dynamic()
   }
   // dynamic (yaapt.py:321-370)
@@ -1076,7 +1098,7 @@ using namespace sat;
 static size_t yaapt_ws_floats(const Plan& P, int B) {
   const size_t nf = P.nframes;
   return (size_t)B * (2 * (size_t)P.Lz + 3 * nf /*e_raw, energy, vuv*/ + 8 * nf /*cand*/ + nf /*spec*/ + 4 /*scal*/ +
-                      2 * nf /*fmean*/ + 4 * nf /*tp, tm*/ + (size_t)SPEC_MAGP * nf /*magnitude windows*/) + 2 * FFT_N /*staged twiddles*/ + 8 + 64;
+                      2 * nf /*fmean*/ + 4 * nf /*tp, tm*/ + 2 * NC * nf /*refined*/ + (size_t)SPEC_MAGP * nf /*magnitude windows*/) + 2 * FFT_N /*staged twiddles*/ + 8 + 64;
 }
 
 extern "C" size_t sat_yaapt_workspace_bytes(const sat_yaapt_plan* plan, int B) {
@@ -1106,6 +1128,12 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   SAT_REQUIRE(P.median_value >= 1 && P.median_value <= 7 && (P.median_value & 1), "yaapt: median_value must be odd <= 7");
   SAT_REQUIRE(P.nframes >= 4 && P.nframes <= 2048, "yaapt: %d frames not supported (4..2048, i.e. up to ~40 s)", P.nframes);
   SAT_REQUIRE(P.tda_nframes == P.nframes, "yaapt: tda frame count differs from the analysis frame count");
+  // frame_space > frame_length: the reference fails on a negative zero extension of spec_track (yaapt.py:206-210)
+  SAT_REQUIRE(P.nframe_size + (P.nframes - 1) * P.frame_jump >= P.L,
+              "yaapt: frame_space too long for frame_length: the last spectral frame ends at sample %d of the %d padded ones "
+              "(the reference fails on the negative zero extension of spec_track)", P.nframe_size + (P.nframes - 1) * P.frame_jump, P.L);
+  SAT_REQUIRE(P.L == P.n + 2 * P.pad && P.Lz >= P.L && P.Lz >= P.nframe_size + (P.nframes - 1) * P.frame_jump,
+              "yaapt: plan lengths inconsistent (L = n + 2 pad, Lz covers the padded signal and the last spectral frame)");
   SAT_REQUIRE_WORKSPACE(workspace_bytes >= sat_yaapt_workspace_bytes(plan, B), "yaapt: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const size_t nf = P.nframes;
@@ -1120,6 +1148,7 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   float* fmean = w;           w += (size_t)B * 2 * nf;
   float* tp = w;              w += (size_t)B * 2 * nf;
   float* tm = w;              w += (size_t)B * 2 * nf;
+  float* refined = w;         w += (size_t)B * 2 * NC * nf;
   float* magbuf = w;          w += (size_t)B * nf * SPEC_MAGP;
   w += (4 - ((uintptr_t)w / 4) % 4) % 4;                     // 16-byte alignment of the float2 table
   float2* stw = (float2*)w;   w += 2 * FFT_N;
@@ -1159,7 +1188,7 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   hipLaunchKernelGGL(yaapt_nccf_kernel, dim3(P.nframes, 2, B), dim3(256), 0, s, filt, fmean, spec, scal, tp, tm, status, U, P);
   SAT_LAUNCH_CHECK("yaapt_nccf_kernel");
   const size_t dp_lds = (size_t)nf * (2 * NC + 2) * sizeof(float) + nf * (NC + 1);
-  hipLaunchKernelGGL(yaapt_refine_dp_kernel, dim3(B), dim3(64), dp_lds, s, tp, tm, spec, energy, vuv, f0, U, P);
+  hipLaunchKernelGGL(yaapt_refine_dp_kernel, dim3(B), dim3(64), dp_lds, s, tp, tm, spec, energy, vuv, f0, scal, status, refined, U, P);
   SAT_LAUNCH_CHECK("yaapt_refine_dp_kernel");
   return SAT_OK;
 }

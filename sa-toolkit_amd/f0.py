@@ -27,6 +27,12 @@ DEFAULTS = dict(sr=16000.0, frame_length=35.0, tda_frame_length=35.0, frame_spac
                 spec_pitch_min_std=0.05)  # yaapt.py:815-859
 
 
+# frame_space > frame_length can leave the last spectral frame (2 * frame_size samples from the last frame's start) inside the padded
+# signal: the reference then asks torch.zeros for a negative zero extension (yaapt.py:206-210) and fails with a RuntimeError
+NEGATIVE_EXTENSION = ("yaapt: frame_space too long for frame_length: the last spectral frame ends at sample %d of the %d padded ones "
+                      "(the reference fails on the negative zero extension of spec_track)")
+
+
 class YaaptPlan(C.Structure):
     """mirror of sat_yaapt_plan (include/satools_hip.h)"""
     _fields_ = [(k, C.c_int32) for k in (
@@ -62,6 +68,16 @@ def biquad_constants(kind, sample_rate, cutoff, Q=0.707):
 
 
 def make_plan(n, opts):
+    """the plan of `opts` at n samples.  Raises where the reference fails for every signal of that length (a negative zero
+    extension); every other limit is the entry point's to refuse"""
+    P = _derive_plan(n, opts)
+    need = P.nframe_size + (P.nframes - 1) * P.frame_jump
+    if need < P.L:
+        raise _lib.SatError(NEGATIVE_EXTENSION % (need, P.L))
+    return P
+
+
+def _derive_plan(n, opts):
     p = dict(DEFAULTS)
     if "frame_lengtht" in opts and "tda_frame_length" not in opts:   # yaapt.py:802-810
         opts = dict(opts)
@@ -201,9 +217,21 @@ class F0Status:
             # the reference fails inside medfilt/unfold when no frame of an utterance is voiced
             raise RuntimeError("yaapt: no voiced frame in utterance(s) %s (the reference's spec_track fails on an "
                                "empty candidate list)" % (st == 1).nonzero().flatten().tolist())
+        if (st == 4).any():
+            # only through the C ABI's ragged form: yaapt_ragged refuses such rows before the launch
+            raise _lib.SatError("yaapt: tda frame count differs from the analysis frame count in utterance(s) %s"
+                                % (st == 4).nonzero().flatten().tolist())
+        if (st == 3).any():
+            # the reference fails in a tensor operation: as_strided with lag_max - lag_min < 0 rows in crs_corr's stride_matrix
+            # (yaapt.py:594) when the spectral pitch lies outside [f0_min, f0_max] by more than two deviations; or (through the C ABI's
+            # ragged form only) torch.zeros of a negative zero extension (:206-210)
+            raise RuntimeError("yaapt: the reference fails in a tensor operation on utterance(s) %s: an empty lag window (lag_max < lag_min, "
+                               "the spectral pitch lies outside f0_min..f0_max by more than two deviations) or a negative zero extension"
+                               % (st == 3).nonzero().flatten().tolist())
         if (st == 2).any():
             raise AssertionError("ERROR: Negative index in the cross correlation calculation of the pYAAPT time domain "
-                                 "analysis. Please try to increase the value of the \"tda_frame_length\" parameter.")
+                                 "analysis. Please try to increase the value of the \"tda_frame_length\" parameter."
+                                 " [yaapt: utterance(s) %s]" % (st == 2).nonzero().flatten().tolist())
 
 
 def workspace_views(ws, P, B):
@@ -214,7 +242,8 @@ def workspace_views(ws, P, B):
                             ("energy", (B, nf), torch.float32), ("vuv", (B, nf), torch.int32),
                             ("cand", (B, 8, nf), torch.float32), ("spec_pitch", (B, nf), torch.float32),
                             ("scal", (B, 4), torch.float32), ("fmean", (B, 2, nf), torch.float32),
-                            ("tp", (B, 2, nf), torch.float32), ("tm", (B, 2, nf), torch.float32)):
+                            ("tp", (B, 2, nf), torch.float32), ("tm", (B, 2, nf), torch.float32),
+                            ("refined", (B, 12, nf), torch.float32)):       # refine(): pitch[6], merit[6]
         cnt = int(np.prod(shape))
         out[name] = ws[off:off + cnt].view(dt).view(*shape)
         off += cnt
@@ -235,6 +264,13 @@ def yaapt_ragged(wav, lengths, opts, defer_status=False):
     dims = [length_dims(P, n) for n in lens]
     if max(d[2] for d in dims) > P.nframes or max(d[1] for d in dims) > P.Lz:
         raise _lib.SatError("yaapt_ragged: an utterance exceeds the batch plan")
+    short = [i for i, d in enumerate(dims) if P.nframe_size + (d[2] - 1) * P.frame_jump < d[1]]
+    if short:      # like make_plan, per utterance: the reference fails on each of them
+        d = dims[short[0]]
+        raise _lib.SatError("yaapt_ragged: utterance(s) %s: " % short + NEGATIVE_EXTENSION[7:] % (P.nframe_size + (d[2] - 1) * P.frame_jump, d[1]))
+    odd = [i for i, d in enumerate(dims) if d[3] != d[2]]
+    if odd:        # as the entry point requires of a single utterance (tda_frame_length above frame_length, at some lengths)
+        raise _lib.SatError("yaapt_ragged: utterance(s) %s: tda frame count differs from the analysis frame count" % odd)
     hann, kaiser, tw = _get_tables(P, wav.device)
     ws_bytes = lib().sat_yaapt_workspace_bytes(C.byref(P), B)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=wav.device)

@@ -7,6 +7,9 @@ Every catalogue case inside the entry point's 4..2048 frames goes through the re
 (satools/hifigan/yaapt.py:946-951, one thread as that module sets on import).  Data only is written:
   fx_f0_edges.npz    <case name>         the F0 track [1, nframes], float32              (the reference returned)
                      raised/<case name>  the exception's type name as a string, else ""  (every case)
+  fx_f0_options.npz  the same two entries for every (case, option set) pair of yaapt_cases.recorded_cases(), each run with the
+                     options of its set, and
+                     assert/<case name>  whether the raised error's text names the reference's `assert N > 0` of crs_corr
 A torch.jit.script function reports a Python-level assert or a failed tensor operation as its own exception classes;
 what is recorded is the name of the first class in the raised exception's MRO that the builtins know (RuntimeError for
 torch.jit.Error), which is what a caller can catch without importing torch internals."""
@@ -51,6 +54,25 @@ def main():
               + ("" if raised == want else f"   !! the catalogue says {want!r}"))
     np.savez_compressed(os.path.join(GOLD, "fx_f0_edges.npz"), **out)
     print("wrote fx_f0_edges.npz:", os.path.getsize(os.path.join(GOLD, "fx_f0_edges.npz")), "bytes")
+
+    # the option sets: every (case, set) pair of the catalogue, the ones the reference raises on included
+    out = {}
+    for case in yaapt_cases.recorded_cases():
+        wav = case.wav().unsqueeze(0)
+        try:
+            track = ref_yaapt.yaapt(wav, dict(case.opts))
+            raised, message = "", ""
+            out[case.name] = track.numpy().astype(np.float32)
+            assert case.nframes is None or out[case.name].shape == (1, case.nframes), (case, out[case.name].shape)
+        except Exception as e:                           # noqa: BLE001  (the type is the recorded result)
+            raised, message = builtin_name(e), str(e)
+        out["raised/" + case.name] = np.array(raised)
+        # a scripted function reports a Python assert as torch.jit.Error (a RuntimeError) whose text names the original class
+        out["assert/" + case.name] = np.array("AssertionError: ERROR: Negative index in the cross correlation" in message)
+        print(f"{case.name:48s} raised={raised!r:16s} voiced frames={int((out[case.name] > 0).sum()) if not raised else '-'}"
+              + (f"   {message.strip().splitlines()[-1][:100]}" if raised else ""))
+    np.savez_compressed(os.path.join(GOLD, "fx_f0_options.npz"), **out)
+    print("wrote fx_f0_options.npz:", os.path.getsize(os.path.join(GOLD, "fx_f0_options.npz")), "bytes")
 
 
 if __name__ == "__main__":

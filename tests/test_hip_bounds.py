@@ -430,13 +430,25 @@ def _(B, c_bn, T, T_f0, n_spk):
 YAAPT_OPTS = {"frame_length": 35.0, "frame_space": 20.0, "nccf_thresh1": 0.25, "tda_frame_length": 25.0}
 
 
-def _yaapt_case(B, n, ragged):
+def _yaapt_row_len(plan, v):
+    """the largest length <= v that may be a row of a batch under the plan's options: the zero extension of its last spectral frame is
+    not negative and its tda frames equal its analysis frames (any length under YAAPT_OPTS).  The others are refused by f0.yaapt_ragged
+    and flagged by the kernels (status 3 / 4); tests/test_hip_yaapt_options.py runs such rows through the C entry point"""
+    from satools_amd import f0 as f0_hip
+    while True:
+        _, L, nf, nt = f0_hip.length_dims(plan, v)
+        if nt == nf and plan.nframe_size + (nf - 1) * plan.frame_jump >= L:
+            return v
+        v -= 1
+
+
+def _yaapt_case(B, n, ragged, opts=YAAPT_OPTS, statuses=(0,)):
     from satools_amd import f0 as f0_hip
     from satools_amd import synthetic
     c = Case()
-    plan = f0_hip.make_plan(n, dict(YAAPT_OPTS))
+    plan = f0_hip.make_plan(n, dict(opts))
     wav = synthetic.harm_batch(list(range(B)), n)
-    lens = [n - 1237 * b for b in range(B)]
+    lens = [_yaapt_row_len(plan, n - 1237 * b) for b in range(B)]
     if ragged:
         for b in range(B):
             wav[b, lens[b]:] = 0.0
@@ -467,7 +479,7 @@ def _yaapt_case(B, n, ragged):
     c.call = call
 
     def ref(t):          # a whole pipeline: the plain call is its reference (property E); here only that it tracked something
-        assert not t["status"].cpu().any() and bool(torch.isfinite(t["f0"]).all())
+        assert set(t["status"].cpu().tolist()) == set(statuses) and bool(torch.isfinite(t["f0"]).all())
     c.ref = ref
     return c
 
@@ -480,6 +492,27 @@ def _(B, n):
 @row("sat_yaapt_ragged_f32", "harmonic", [(1, 8000), (3, 16123)])
 def _(B, n):
     return _yaapt_case(B, n, True)
+
+
+# the option sets of tests/yaapt_cases.py that move a buffer extent or a loop limit (the plan fields are asserted on the CPU by
+# tests/test_yaapt_cases_host.py): nframe_size 1280 with an overlap of 128; tda_len 1024 (lengths with n mod 896 in 384..640: the
+# reference's zero extension is not negative and the tda frames equal the analysis frames); an overlap of 1; short frames; 8 kHz; the
+# largest harmonic count; and the set whose NCCF windows are empty (status 2: the kernel's guard, not its loops, must hold)
+def _yaapt_option_rows(set_name, shapes, statuses=(0,)):
+    def opts():
+        import yaapt_cases
+        return yaapt_cases.option_set(set_name).opts
+    for entry, ragged in (("sat_yaapt_f32", False), ("sat_yaapt_ragged_f32", True)):
+        row(entry, "harmonic/" + set_name, shapes)(lambda B, n, ragged=ragged: _yaapt_case(B, n, ragged, opts(), statuses))
+
+
+_yaapt_option_rows("jump512_ov128", [(1, 8192), (3, 16901)])
+_yaapt_option_rows("tda1024", [(1, 9 * 896 + 512), (3, 18 * 896 + 400)])
+_yaapt_option_rows("ov1", [(1, 8000), (3, 16123)])
+_yaapt_option_rows("short", [(1, 8000), (3, 16123)])
+_yaapt_option_rows("sr8000", [(1, 8000), (3, 16123)])
+_yaapt_option_rows("nharm6_f0max250", [(1, 8000), (3, 16123)])
+_yaapt_option_rows("status2", [(1, 8000), (3, 16123)], statuses=(2,))      # the float32 oracle asserts on every row and length
 
 
 # ---- wav2vec2 support (csrc/w2v2.hip) ----------------------------------------------------------------------------------------------

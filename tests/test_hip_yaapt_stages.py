@@ -9,6 +9,7 @@ INTERMEDIATES, so a wrong stage is named and the stages after it are not blamed 
 
 EXACT (torch.equal, NaN = NaN): `filt` against oracle/biquad.py with its zero extension; `vuv` against the device energy;
 the default candidates of unvoiced frames; `spec_pitch` and `pitch_std` against oracle.spec_select(device candidates);
+the six refined pitch and merit rows against oracle.refine(device tp, tm, spec_pitch, energy, vuv);
 the final track against oracle.dynamic(oracle.refine(device tp, tm, spec_pitch, energy, vuv)) — all-NaN `tm` and a NaN
 `mean_pitch` included —; the final track against the reference's own (tests/golden/fx_f0_edges.npz, frame 0 exempt as in
 tests/test_hip_yaapt.py).
@@ -55,13 +56,15 @@ OPTS = yc.OPTS
 #   sp_mean  window product 1, ceil(n / 256) adds per thread, 8 for the block reduction (the division is counted there)
 #   shc_sum  the SHC window: n sequential adds (the harmonic products are counted there)
 #   shc_avg  block_sum256 over the peak range
-#   fm_head  x - previous mean 1, v0 + v1 1, six shuffle levels;  fm_tail: ceil(n / 64) adds per lane, six shuffle levels
-#   dot      the NCCF's four FMA accumulators: ceil(n / 4) fused steps each, then (n0 + n1) + (n2 + n3)
+#   fm_head  x - previous mean 1, v0 + v1 1, six shuffle levels (two loads per lane whatever the overlap: it is at most 128);
+#            fm_tail: ceil(n / 64) adds per lane, six shuffle levels, n = frame_jump
+#   dot      the NCCF's four FMA accumulators: n // 4 fused steps each and the n % 4 left-over terms on the FIRST one (its tail loop),
+#            then (n0 + n1) + (n2 + n3).  n = tda_len - lag_max follows the data, so n % 4 takes every value under any plan
 #   pw       block_sum256 of d * d: product and add per term, ceil(n / 256) terms per thread, 8 for the reduction
 _c = math.ceil
 DEVICE = r64.Roundings(cmul=3.25, hyp=4, nl_sum=lambda n: _c(n / 256) + 8, en_mean=lambda n: _c(n / 256) + 8,
                        sp_mean=lambda n: _c(n / 256) + 9, shc_sum=lambda n: n, shc_avg=lambda n: _c(n / 256) + 8,
-                       fm_head=lambda n: 8, fm_tail=lambda n: _c(n / 64) + 6, dot=lambda n: _c(n / 4) + 2,
+                       fm_head=lambda n: 8, fm_tail=lambda n: _c(n / 64) + 6, dot=lambda n: n // 4 + n % 4 + 2,
                        pw=lambda n: 2 * _c(n / 256) + 8)
 
 _RATIOS, _EXEMPT, _T0 = {}, {}, time.time()
@@ -98,7 +101,7 @@ def device_run(case):
     """-> (f0 [nframes], {name: cpu tensor of utterance 0}) of ONE `yaapt(..., return_aux=True)` call, kept for the batch tests"""
     from satools_amd import f0 as f0_hip
     if case.name not in _RUNS:
-        f0, aux = f0_hip.yaapt(case.wav().unsqueeze(0).to(DEV), OPTS, return_aux=True)
+        f0, aux = f0_hip.yaapt(case.wav().unsqueeze(0).to(DEV), case.opts, return_aux=True)
         _RUNS[case.name] = (f0.cpu()[0], {k: v.cpu()[0] for k, v in aux.items()})
     return _RUNS[case.name]
 
@@ -122,22 +125,29 @@ def _ranges(frames):
     return ", ".join(out)
 
 
-def _note(stage, case, res):
+def _note(stage, case, res, ratios=None, exempt=None, key=None):
+    ratios, exempt = (_RATIOS if ratios is None else ratios), (_EXEMPT if exempt is None else exempt)
     r = res["ratio"]
     print(f"  {stage:10s} error / bound {r:8.4f}" + (f"   exempt {res['exempt']}" if res.get("exempt") else "")
           + (f"   unbounded {res['unbounded']}" if res.get("unbounded") else ""))
-    if r > _RATIOS.get(stage, (-1.0, ""))[0]:
-        _RATIOS[stage] = (r, case.name)
-    for key in ("exempt", "unbounded"):
-        if res.get(key):
-            _EXEMPT.setdefault(case.name, {})[stage + ("" if key == "exempt" else "/unbounded")] = _ranges(res[key])
+    if r > ratios.get(key or stage, (-1.0, ""))[0]:
+        ratios[key or stage] = (r, case.name)
+    for k in ("exempt", "unbounded"):
+        if res.get(k):
+            exempt.setdefault(case.name, {})[stage + ("" if k == "exempt" else "/unbounded")] = _ranges(res[k])
 
 
 @pytest.mark.parametrize("case", yc.accepted(), ids=repr)
 def test_every_stage_from_the_devices_own_upstream(case, gold):
+    check_every_stage(case, gold.npz("fx_f0_edges.npz"))
+
+
+def check_every_stage(case, fx, note=_note):
+    """the stage checks of one accepted case under ITS option set (`case.opts`: the catalogue's cases carry OPTS, the (case, set) pairs
+    of tests/test_hip_yaapt_options.py their set), against the reference tracks of the fixture `fx`"""
     from oracle import biquad
     from oracle import yaapt as oy
-    plan = oy.Plan(case.n, OPTS)
+    plan = oy.Plan(case.n, case.opts)
     f0, g = device_run(case)
     nf = plan.nframes
     assert f0.shape == (nf,) and case.nframes == nf
@@ -149,7 +159,7 @@ def test_every_stage_from_the_devices_own_upstream(case, gold):
     x = np.concatenate([np.zeros(plan.pad, np.float32), case.wav().numpy(), np.zeros(plan.pad, np.float32)])
     filt = g["filt"].numpy()
     for sig, v in ((0, x), (1, x * x)):
-        ref = biquad.band_limit(v)
+        ref = biquad.band_limit(v, int(plan.fs), plan.p["bp_low"], plan.p["bp_high"])
         assert np.array_equal(filt[sig, :plan.L], ref), ("filt", sig, int((filt[sig, :plan.L] != ref).sum()))
         assert not filt[sig, plan.L:].any(), ("filt zero extension", sig)
     assert torch.equal(vuv, energy > plan.p["nlfer_thresh1"]), "vuv"
@@ -161,9 +171,12 @@ def test_every_stage_from_the_devices_own_upstream(case, gold):
     tp1, tm1 = torch.cat((g["tp"][0:1], z)), torch.cat((g["tm"][0:1], z))
     tp2, tm2 = torch.cat((g["tp"][1:2], z)), torch.cat((g["tm"][1:2], z))
     rp, rm = oy.refine(tp1, tm1, tp2, tm2, spec.clone(), energy, vuv, plan)
+    # refine() itself, row by row (the final track shows one row per frame; `merit_pivot`, for one, never shows in it: at a frame with
+    # energy <= nlfer_thresh2 every row it fills has pitch 0)
+    assert same(g["refined"][:6], rp), ("refined pitch", torch.nonzero(torch.nan_to_num(g["refined"][:6]) != torch.nan_to_num(rp))[:8].tolist())
+    assert same(g["refined"][6:], rm), ("refined merit", torch.nonzero(torch.nan_to_num(g["refined"][6:]) != torch.nan_to_num(rm))[:8].tolist())
     want_f0 = oy.dynamic(rp, rm, energy, plan)
     assert same(f0, want_f0), ("final f0", torch.nonzero(f0 != want_f0).flatten()[:8].tolist())
-    fx = gold.npz("fx_f0_edges.npz")
     assert str(fx["raised/" + case.name]) == ""
     ref_track = torch.from_numpy(fx[case.name][0])
     assert torch.equal(f0[1:], ref_track[1:]), ("reference track", torch.nonzero(f0 != ref_track).flatten()[:8].tolist())
@@ -189,7 +202,7 @@ def test_every_stage_from_the_devices_own_upstream(case, gold):
         res[f"nccf{sig + 1}"] = r64.judge_nccf(filt[sig], fm, spec.numpy(), float(pstd), g["tp"][sig].numpy(),
                                               g["tm"][sig].numpy(), plan, DEVICE)
     for stage, r in res.items():
-        _note(stage, case, r)
+        note(stage, case, r)
     for stage, r in res.items():
         assert not r.get("wrong"), (stage, r["wrong"][:4])
         assert r["ratio"] <= 1.0, (stage, r["ratio"])

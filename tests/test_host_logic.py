@@ -169,6 +169,44 @@ def test_yaapt_plan_matches_the_oracle_plan():
     assert np.allclose(list(P.hp), [float(v) for v in biquad.kernel_constants("hp", 16000, 1500.0)], rtol=0, atol=0)
 
 
+def test_yaapt_plan_matches_the_oracle_plan_under_every_option_set():
+    """f0.make_plan against oracle.yaapt.Plan, field by field, for every option set of tests/yaapt_cases.py (the refused ones too:
+    the plan is what the entry point refuses) and for the `frame_lengtht` spelling; `length_dims` against a full plan; and
+    make_plan's own refusal, where the reference fails on a negative zero extension whatever the signal"""
+    import yaapt_cases as yc
+    from oracle import biquad
+    from oracle import yaapt as oy
+    ints = ("pad", "L", "nfft", "frame_size", "frame_jump", "nframes", "nl_lo", "nl_hi", "nframe_size", "half_wl", "wl", "max_shc", "min_shc",
+            "nharm", "maxpeaks", "pk_center", "pk_min_lag", "pk_max_lag", "tda_len", "tda_nframes", "maxcands", "nccf_center", "median_value")
+    scalars = ("nlfer_thresh1", "nlfer_thresh2", "shc_thresh1", "shc_thresh2", "f0_double", "f0_half", "merit_extra", "dp5_k1", "f0_min", "f0_max",
+               "spec_pitch_min_std", "nccf_thresh1", "nccf_thresh2", "merit_pivot", "dp_w1", "dp_w2", "dp_w3", "dp_w4")
+    sets = [(s.name, s.opts, [c.n for c in s.cases]) for s in yc.OPTION_SETS]
+    sets.append(("frame_lengtht", {"frame_lengtht": 22.0, "frame_space": 15.0}, [20480]))
+    sets.append(("both spellings", {"frame_lengtht": 22.0, "tda_frame_length": 24.0, "frame_space": 18.0}, [20480]))
+    for name, opts, lengths in sets:
+        for n in lengths + [lengths[0] + 1, lengths[0] // 2 + 3]:
+            Q = oy.Plan(n, opts)
+            P = f0._derive_plan(n, dict(opts))          # make_plan without its own refusal (below)
+            for k in ints:
+                assert getattr(P, k) == getattr(Q, k), (name, n, k, getattr(P, k), getattr(Q, k))
+            for k in scalars:
+                assert getattr(P, k) == np.float32(Q.p[k]), (name, n, k)
+            assert (P.n, P.fs, P.delta, P.Lz) == (n, np.float32(Q.fs), np.float32(Q.delta), max(Q.L, Q.need)), (name, n)
+            assert P.inv_shc_thresh1 == np.float32(1 / Q.p["shc_thresh1"]) and P.merit_boost1 == np.float32(1 + Q.p["merit_boost"])
+            assert list(P.lp) == [float(v) for v in biquad.kernel_constants("lp", int(Q.fs), Q.p["bp_low"])], name
+            assert list(P.hp) == [float(v) for v in biquad.kernel_constants("hp", int(Q.fs), Q.p["bp_high"])], name
+            big = f0._derive_plan(3 * n, dict(opts))
+            assert f0.length_dims(big, n) == [P.n, P.L, P.nframes, P.tda_nframes], (name, n)
+            if Q.need < Q.L:
+                with pytest.raises(_lib.SatError, match="frame_space too long for frame_length"):
+                    f0.make_plan(n, dict(opts))
+            else:
+                assert bytes(f0.make_plan(n, dict(opts))) == bytes(P)
+    assert oy.Plan(20480, {"frame_lengtht": 22.0}).tda_len == 352 and oy.Plan(20480, {"frame_lengtht": 22.0, "tda_frame_length": 24.0}).tda_len == 384
+    s = yc.option_set("space_gt_frame")
+    assert oy.Plan(s.cases[0].n, s.opts).need < oy.Plan(s.cases[0].n, s.opts).L
+
+
 def test_fbank_tables_match_the_oracle():
     from oracle import fbank as ofb
     from satools_amd import asrbn

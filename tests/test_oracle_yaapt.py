@@ -60,6 +60,30 @@ def test_edge_catalogue_matches_the_reference(gold):
         assert np.array_equal(final.numpy()[1:], ref[0, 1:]), (case, np.flatnonzero(final.numpy() != ref[0]).tolist())
 
 
+def test_option_sets_match_the_reference(gold):
+    """the same terms under every option set of tests/yaapt_cases.py (fx_f0_options.npz): equal tracks, frame 0 exempt, and a raise
+    where the reference raises.  The reference is a scripted function: its failed `assert N > 0` arrives as torch.jit.Error, a
+    RuntimeError whose text names AssertionError (`assert/<case>` in the fixture); the restatement, plain Python, raises the
+    AssertionError itself.  The two other failures are RuntimeErrors on both sides: torch.zeros of a negative zero extension
+    (frame_space > frame_length), and a negative number of lags (the spectral pitch above f0_max by more than two deviations)"""
+    import yaapt_cases as yc
+    fx = gold.npz("fx_f0_options.npz")
+    cases = yc.recorded_cases()
+    assert sorted(k for k in fx.files if k.startswith("raised/")) == sorted("raised/" + c.name for c in cases)
+    assert sum(1 for c in cases if c.raises) == 3
+    for case in cases:
+        _, final, raised = yc.oracle_run(case)
+        ref_raised, ref_assert = str(fx["raised/" + case.name]), bool(fx["assert/" + case.name])
+        assert raised == (case.raises or ""), (case, raised)
+        assert ref_raised == ("RuntimeError" if raised else "") and ref_assert == (raised == "AssertionError"), (case, raised, ref_raised)
+        if raised:
+            assert case.name not in fx.files
+            continue
+        ref = fx[case.name]
+        assert ref.shape == (1, case.nframes), case
+        assert np.array_equal(final.numpy()[1:], ref[0, 1:]), (case, np.flatnonzero(final.numpy() != ref[0]).tolist())
+
+
 def test_spec_track_is_its_two_halves():
     """spec_candidates + spec_select compose to spec_track bit for bit, NaN deviation included"""
     import yaapt_cases as yc

@@ -24,12 +24,12 @@ MIN_FRAMES, MAX_FRAMES = 4, 2048          # sat_yaapt_f32 accepts 4..2048 frames
 DEFINITELY_UNVOICED = 0.1                 # nlfer_thresh2 (default): refine() discards the candidates of such a frame
 
 
-def tone(n, on0=0, on1=None, gain=1.0, clip=None):
+def tone(n, on0=0, on1=None, gain=1.0, clip=None, f0=120.0, sr=SR):
     """the harmonic tone, gated to [on0, on1), optionally amplified and clipped to +-clip"""
-    t = np.arange(n, dtype=np.float64) / SR
+    t = np.arange(n, dtype=np.float64) / sr
     x = np.zeros(n, dtype=np.float64)
     for k in range(1, 6):
-        x += 0.3 / k * np.sin(2 * np.pi * k * 120.0 * t)
+        x += 0.3 / k * np.sin(2 * np.pi * k * f0 * t)
     gate = np.zeros(n, dtype=np.float64)
     gate[on0:n if on1 is None else on1] = 1.0
     x = x * gate * gain
@@ -56,8 +56,9 @@ class Case:
     no such frame"""
 
     def __init__(self, name, kind, make, n, nframes, vuv=None, nv=None, std_nan=False, mean_nan=None, raises=None,
-                 refused=False, exact_only=False, underflows=False):
+                 refused=False, exact_only=False, underflows=False, opts=None):
         self.name, self.kind, self.make, self.n, self.nframes = name, kind, make, n, nframes
+        self.opts = OPTS if opts is None else opts          # the option set of the (case, set) pairs further down
         self.vuv, self.nv, self.std_nan, self.mean_nan = vuv, nv, std_nan, mean_nan
         self.raises, self.refused, self.exact_only, self.underflows = raises, refused, exact_only, underflows
 
@@ -177,7 +178,7 @@ def oracle_run(case):
     if case.name not in _ORACLE:
         aux = {}
         try:
-            final, raised = oy.yaapt_one(case.wav(), OPTS, aux=aux), ""
+            final, raised = oy.yaapt_one(case.wav(), case.opts, aux=aux), ""
         except Exception as e:                      # noqa: BLE001  (the type is the property under test)
             final, raised = None, type(e).__name__
         _ORACLE[case.name] = (aux, final, raised)
@@ -205,7 +206,7 @@ def judge_oracle(aux, plan, R):
 def judged_oracle(case, R):
     from oracle import yaapt as oy
     if case.name not in _JUDGED:
-        _JUDGED[case.name] = judge_oracle(oracle_run(case)[0], oy.Plan(case.n, OPTS), R)
+        _JUDGED[case.name] = judge_oracle(oracle_run(case)[0], oy.Plan(case.n, case.opts), R)
     return _JUDGED[case.name]
 
 
@@ -232,3 +233,216 @@ def assert_exempt_cap(case, res, energy):
     for k in unbounded:
         assert float(energy[k]) <= DEFINITELY_UNVOICED, (case, k, float(energy[k]))
     return ex
+
+
+# ======================================================================================================================
+# OPTION SETS.  Every case above runs under OPTS, i.e. ONE plan (frame_size 560, frame_jump 320, tda_len 400 with an overlap of 80,
+# nharm 3, median 7, max_shc 256, wl 21, bins 60..205, every scalar at one value).  The table below moves the plan: each set names
+# the edge it is there for and the plan fields that put it there (asserted from oracle.yaapt.Plan by the host test, so a typo cannot
+# move a set off its edge), and carries two or three signals of its own: a tone whose frame count sits on a lane edge for the set's
+# jump, a clipped or noisy one, and for the limit sets a burst with few voiced frames.
+#   accepted   the reference runs (tests/golden/fx_f0_options.npz holds its tracks), the device must agree stage by stage
+#   wiring     one scalar option changed against OPTS; `observe` names the oracle intermediate (or the final track) that changes on
+#              the set's signal, so that a kernel which ignores the option fails
+#   refused    outside the entry point's region of plans: `refused` is the message of the requirement that refuses it
+#   status 2   every frame's NCCF window is empty (N = tda_len - lag_max <= 0): the reference asserts, the device reports status 2
+# A case of a set is named "<set>/<signal>".
+# ======================================================================================================================
+def two_level(n, sr=SR):
+    """the tone, its second half at 0.3 of the level: frames with a normalised energy between nlfer_thresh2 and nlfer_thresh1"""
+    return torch.cat((tone(n, sr=sr)[:n // 2], 0.3 * tone(n, sr=sr)[n // 2:]))
+
+
+def two_pitch(n, sr=SR):
+    """150 Hz, then 100 Hz: spectral candidates that disagree from frame to frame (the Viterbi costs decide).  (120 Hz then 200 Hz
+    widens `pitch_std` to 40 Hz and with it the lag window of frame 0, most of which is padding: its NCCF is flat to within the
+    float64 bound, an exempt frame)"""
+    return torch.cat((tone(n, f0=150.0, sr=sr)[:n // 2], tone(n, f0=100.0, sr=sr)[n // 2:]))
+
+
+def noisy_tone(seed, n):
+    """the tone under white noise: NCCF frames whose first local peak is not the largest within nccf_pwidth (nccf_thresh2 decides),
+    and outliers in the best track that each median width smooths differently (a clean tone's track is constant: any width passes)"""
+    return 0.5 * tone(n) + 0.3 * (2.0 * noise(seed, n) - 1.0)
+
+
+SIGNALS = {
+    "tone": ("tone", lambda n, sr: tone(n, sr=sr)),
+    "tone200": ("tone", lambda n, sr: tone(n, f0=200.0, sr=sr)),
+    "tone170": ("tone", lambda n, sr: tone(n, f0=170.0, sr=sr)),
+    "clip40": ("clip", lambda n, sr: tone(n, gain=40.0, clip=1.0, sr=sr)),
+    "clip100": ("clip", lambda n, sr: tone(n, gain=100.0, clip=1.0, sr=sr)),
+    "level": ("tone", two_level),
+    "jump": ("tone", two_pitch),
+    "noisy1": ("noise", lambda n, sr: noisy_tone(1, n)),
+    "noisy2": ("noise", lambda n, sr: noisy_tone(2, n)),
+    # (the seeds: those whose float32 decisions all clear the float64 bounds under their set, tests/test_yaapt_cases_host.py)
+    "noisy4": ("noise", lambda n, sr: noisy_tone(4, n)),
+    "noisy9": ("noise", lambda n, sr: noisy_tone(9, n)),
+    "rand0": ("noise", lambda n, sr: noise(0, n)),
+}
+
+
+class OptionSet:
+    """name, opts (handed to yaapt as they are), why = the edge in words, fields = the plan fields that put the set there (`ov` =
+    tda_len - frame_jump), signals = [(signal name, n) | ("burst", length, at, n)]; refused = regex of the entry point's message (its
+    one case is what the refusal is tried on); wiring = (key, observe); raises = {signal: exception type}"""
+
+    def __init__(self, name, opts, why, fields=None, signals=(), refused=None, wiring=None, raises=None):
+        self.name, self.opts, self.why, self.fields = name, opts, why, dict(fields or {})
+        self.refused, self.wiring = refused, wiring
+        self.raises = dict(raises or {})           # signal name -> the oracle's exception type (the reference's: see the fixture)
+        self.cases = [self._case(s) for s in signals]
+
+    def _case(self, s):
+        from oracle import yaapt as oy
+        sr = float(self.opts.get("sr", SR))
+        if s[0] == "burst":
+            _, length, at, n = s
+            name, kind, make = f"burst{length}_at{at}_of{n}", "burst", (lambda: tone(n, at, at + length, sr=sr))
+        else:
+            sig, n = s
+            kind, fn = SIGNALS[sig]
+            name, make = f"{sig}_{n}", (lambda: fn(n, sr))
+        return Case(f"{self.name}/{name}", kind, make, n, oy.Plan(n, self.opts).nframes, opts=self.opts, raises=self.raises.get(name),
+                    refused=self.refused is not None)
+
+    def __repr__(self):
+        return self.name
+
+
+def _o(**kw):
+    return {**OPTS, **{k: float(v) for k, v in kw.items()}}
+
+
+ALL_SCALARS = dict(nlfer_thresh1=0.7, nlfer_thresh2=0.15, shc_thresh1=4.5, shc_thresh2=1.3, f0_double=160.0, f0_half=140.0, dp5_k1=9.0,
+                   nccf_thresh1=0.3, nccf_thresh2=0.85, merit_boost=0.25, merit_pivot=0.95, merit_extra=0.45, dp_w1=0.2, dp_w2=0.45,
+                   dp_w3=0.15, dp_w4=0.8, spec_pitch_min_std=0.06)
+
+OPTION_SETS = [
+    # ---- the plan's extents --------------------------------------------------------------------------------------------
+    OptionSet("jump512_ov128", _o(frame_length=40, frame_space=32, tda_frame_length=40),
+              "nframe_size = 1280 = 5 * 256 (the whole magnitude hand-over and kaiser loop), overlap 128 (the second head load of "
+              "yaapt_frame_means_kernel in full)", dict(frame_size=640, nframe_size=1280, frame_jump=512, tda_len=640, ov=128),
+              [("tone", 64 * 512 + 1), ("clip40", 63 * 512), ("burst", 1536, 28160, 63 * 512)]),
+    OptionSet("tda1024", _o(frame_length=40, frame_space=56, tda_frame_length=64),
+              "tda_len = 1024: the whole of d[1024] / phi[1024]; frame_space > frame_length, at lengths where the reference's zero "
+              "extension is not negative and the tda frames equal the analysis frames (n mod 896 in 384..640)",
+              dict(frame_size=640, nframe_size=1280, frame_jump=896, tda_len=1024, ov=128),
+              [("tone", 64 * 896 + 512), ("clip40", 62 * 896 + 384), ("burst", 2688, 12288, 19 * 896 + 640)]),
+    OptionSet("ov1", _o(tda_frame_length=20.0625), "overlap 1: one head sample per frame", dict(tda_len=321, frame_jump=320, ov=1),
+              [("tone", 20481), ("clip40", 20160)]),
+    OptionSet("short", _o(frame_length=20, frame_space=10, tda_frame_length=17), "short frames, overlap 112, 128 / 129 frames",
+              dict(frame_size=320, nframe_size=640, frame_jump=160, tda_len=272, ov=112), [("tone200", 20480), ("clip40", 20481)]),
+    OptionSet("sr8000", _o(sr=8000, f0_max=140), "8 kHz: every length halves, delta halves (wl 41, pk_center 26)",
+              dict(frame_size=280, frame_jump=160, tda_len=200, wl=41, pk_center=26, nframe_size=560),
+              [("tone", 64 * 160), ("clip40", 64 * 160 + 1)]),
+    OptionSet("sr22050", _o(sr=22050, frame_length=25, frame_space=15, tda_frame_length=20),
+              "22.05 kHz: odd frame size and jump, the unaligned prefilter path by construction",
+              dict(frame_size=551, frame_jump=330, tda_len=441, ov=111, pad=275), [("tone", 64 * 330 + 1), ("clip100", 63 * 330)]),
+    # ---- harmonics, median, ranges ---------------------------------------------------------------------------------------
+    OptionSet("nharm1", _o(shc_numharms=1), "one harmonic product", dict(nharm=1), [("tone", 20481), ("clip40", 20160)]),
+    OptionSet("nharm4_f0max350", _o(shc_numharms=4, f0_max=350), "four harmonics, a narrower SHC range",
+              dict(nharm=4, max_shc=230, pk_max_lag=192), [("tone", 20480), ("clip40", 20481)]),
+    OptionSet("nharm6_f0max250", _o(shc_numharms=6, f0_max=250),
+              "the largest harmonic count the 1280-float magnitude window admits on signals the reference runs on: "
+              "max_shc * (nharm + 1) + wl = 179 * 7 + 21 = 1274 <= 1280 (7 harmonics need f0_max <= 206, where the reference "
+              "fails on the catalogue's signals: see nharm7_f0max200)", dict(nharm=6, max_shc=179),
+              [("tone", 20481), ("clip40", 20160), ("burst", 960, 17600, 20480)]),
+    OptionSet("median1", _o(median_value=1), "median width 1 (and 1 in spec_track)", dict(median_value=1), [("tone", 20481), ("clip40", 20160), ("noisy4", 20481)]),
+    OptionSet("median3", _o(median_value=3), "median width 3 (1 in spec_track)", dict(median_value=3), [("tone", 20480), ("noisy1", 20481)]),
+    OptionSet("median5", _o(median_value=5), "median width 5 (3 in spec_track)", dict(median_value=5), [("tone", 20160), ("noisy9", 20481)]),
+    OptionSet("f0_50_300", _o(f0_min=50, f0_max=300), "NLFER bins 50..154, min_shc 26", dict(nl_lo=50, nl_hi=154, min_shc=26),
+              [("tone", 20481), ("clip40", 20160)]),
+    OptionSet("f0min80_pw30_win60", _o(f0_min=80, shc_pwidth=30, shc_window=60), "SHC window 31, peak half-width 8, first lag 32",
+              dict(wl=31, half_wl=15, pk_center=8, pk_min_lag=32), [("tone", 20481), ("clip40", 20160)]),
+    OptionSet("nccf_pwidth9", _o(nccf_pwidth=9), "NCCF peak half-width 4", dict(nccf_center=4), [("tone", 20481), ("noisy2", 20481)]),
+    OptionSet("bandpass", _o(bp_low=80, bp_high=1000), "other biquad coefficients", {}, [("tone200", 20481), ("clip40", 20160)]),
+    OptionSet("all_scalars", {**OPTS, **ALL_SCALARS}, "every threshold and weight off its default at once", {},
+              [("tone", 20481), ("clip40", 20160), ("jump", 20481)]),
+    # ---- wiring: one scalar changed against OPTS, on a signal where the oracle's output changes ------------------------
+    OptionSet("w_nlfer_thresh1", _o(nlfer_thresh1=0.5), "wiring", {}, [("tone", 20481)], wiring=("nlfer_thresh1", "vuv")),
+    OptionSet("w_nlfer_thresh2", _o(nlfer_thresh2=0.5), "wiring", {}, [("level", 20481)], wiring=("nlfer_thresh2", "final")),
+    OptionSet("w_shc_thresh1", _o(shc_thresh1=3.0), "wiring", {}, [("clip40", 20481)], wiring=("shc_thresh1", "final")),
+    OptionSet("w_shc_thresh2", _o(shc_thresh2=2.5), "wiring", {}, [("tone", 20481)], wiring=("shc_thresh2", "cand_merit")),
+    OptionSet("w_f0_double", _o(f0_double=200.0), "wiring", {}, [("tone170", 20481)], wiring=("f0_double", "cand_pitch")),
+    OptionSet("w_f0_half", _o(f0_half=100.0), "wiring", {}, [("tone", 20481)], wiring=("f0_half", "cand_pitch")),
+    OptionSet("w_dp5_k1", _o(dp5_k1=1000.0), "wiring", {},
+              [("jump", 20481)], wiring=("dp5_k1", "final")),
+    OptionSet("w_nccf_thresh1", _o(nccf_thresh1=0.6), "wiring", {}, [("clip40", 20481)], wiring=("nccf_thresh1", "final")),
+    OptionSet("w_nccf_thresh2", _o(nccf_thresh2=0.25), "wiring", {}, [("noisy1", 20481)], wiring=("nccf_thresh2", "tp1+tp2")),
+    OptionSet("w_merit_boost", _o(merit_boost=0.3), "wiring", {}, [("clip40", 20481)], wiring=("merit_boost", "final")),
+    # merit_pivot fills rows of refine() at frames with energy <= nlfer_thresh2; their pitch is 0 in every row but the spectral one, which
+    # costs ~1 there, so the FINAL track does not move with it on any signal tried (level steps, fades, dips around the threshold, noise,
+    # pivots from 0 to 3): the device test compares the refined rows themselves (workspace view "refined")
+    OptionSet("w_merit_pivot", _o(merit_pivot=0.9), "wiring", {}, [("burst", 960, 17600, 20480)], wiring=("merit_pivot", "ref_merit")),
+    OptionSet("w_merit_extra", _o(merit_extra=0.6), "wiring", {}, [("tone", 20481)], wiring=("merit_extra", "cand_merit")),
+    OptionSet("w_dp_w1", _o(dp_w1=5.0), "wiring", {}, [("jump", 20481)], wiring=("dp_w1", "final")),
+    OptionSet("w_dp_w2", _o(dp_w2=0.05), "wiring", {}, [("clip40", 20481)], wiring=("dp_w2", "final")),
+    OptionSet("w_dp_w3", _o(dp_w3=0.6), "wiring", {}, [("clip40", 20481)], wiring=("dp_w3", "final")),
+    OptionSet("w_dp_w4", _o(dp_w4=0.3), "wiring", {}, [("clip40", 20481)], wiring=("dp_w4", "final")),
+    OptionSet("w_spec_pitch_min_std", _o(spec_pitch_min_std=0.2), "wiring", {}, [("clip40", 20481)],
+              wiring=("spec_pitch_min_std", "final")),
+    # ---- the reference raises: the device must end the same way --------------------------------------------------------
+    OptionSet("status2", dict(frame_length=10.0, frame_space=5.0, tda_frame_length=12.0),
+              "tda_len 192: N = tda_len - lag_max <= 0 in the frames of a 120 Hz tone (status 2); a 200 Hz tone has none",
+              dict(tda_len=192, frame_jump=80, frame_size=160), [("tone", 20480), ("tone200", 20480)], raises={"tone_20480": "AssertionError"}),
+    OptionSet("nharm7_f0max200", _o(shc_numharms=7, f0_max=200),
+              "seven harmonics fit the magnitude window below f0_max = 206 only; the SHC of the tone then peaks at its octave, above "
+              "f0_max by more than two deviations: lag_max < lag_min, the reference fails in crs_corr (status 3)", dict(nharm=7, max_shc=153),
+              [("tone", 20480)], raises={"tone_20480": "RuntimeError"}),
+    # ---- refused ---------------------------------------------------------------------------------------------------------
+    OptionSet("reference_defaults", {}, "the reference's own defaults: overlap 400 > 128", dict(tda_len=560, frame_jump=160), signals=[("tone", 20480)],
+              refused="tda_frame_length / frame_space combination not supported"),
+    OptionSet("fft4096", _o(fft_length=4096), "", {}, signals=[("tone", 20480)], refused=r"fft_length 4096 not supported \(8192 only\)"),
+    OptionSet("maxpeaks5", _o(shc_maxpeaks=5), "", {}, signals=[("tone", 20480)], refused="shc_maxpeaks/nccf_maxcands must be 4/3"),
+    OptionSet("maxcands4", _o(nccf_maxcands=4), "", {}, signals=[("tone", 20480)], refused="shc_maxpeaks/nccf_maxcands must be 4/3"),
+    OptionSet("median9", _o(median_value=9), "", {}, signals=[("tone", 20480)], refused="median_value must be odd <= 7"),
+    OptionSet("median4", _o(median_value=4), "", {}, signals=[("tone", 20480)], refused="median_value must be odd <= 7"),
+    OptionSet("frame41", _o(frame_length=41), "nframe_size 1312 > 1280", dict(nframe_size=1312), signals=[("tone", 20480)], refused="frame_length too long for the spectral kernel"),
+    OptionSet("nharm8", _o(shc_numharms=8), "", {}, signals=[("tone", 20480)], refused="shc_numharms out of range"),
+    OptionSet("tda_le_space", _o(tda_frame_length=20), "tda_len == frame_jump", dict(tda_len=320, frame_jump=320), signals=[("tone", 20480)],
+              refused="tda_frame_length / frame_space combination not supported"),
+    OptionSet("space_gt_frame", _o(frame_space=56, tda_frame_length=64),
+              "frame_space > frame_length at a length where the last spectral frame ends inside the padded signal: the reference fails "
+              "on a negative zero extension", dict(frame_jump=896, tda_len=1024), [("tone", 20480)], refused="frame_space too long for frame_length",
+              raises={"tone_20480": "RuntimeError"}),
+]
+
+
+def option_set(name):
+    return next(s for s in OPTION_SETS if s.name == name)
+
+
+def accepted_sets():
+    """the sets the device accepts and the reference runs on (the wiring sets among them)"""
+    return [s for s in OPTION_SETS if not s.refused and not s.raises]
+
+
+def raising_sets():
+    """accepted by the entry point, but the reference raises on (some of) their signals: a status word must say so"""
+    return [s for s in OPTION_SETS if not s.refused and s.raises]
+
+
+def refused_sets():
+    return [s for s in OPTION_SETS if s.refused]
+
+
+def option_cases():
+    """every (case, set) pair the device must agree with the reference on, stage by stage"""
+    return [c for s in OPTION_SETS if not s.refused for c in s.cases if c.raises is None]
+
+
+def recorded_cases():
+    """what tests/golden/make_f0_edge_fixtures.py runs through the reference: every pair of the sets the entry point accepts, and
+    the refused set on which the reference has a word of its own (the other refusals are limits of the device alone)"""
+    return [c for s in OPTION_SETS if not s.refused or s.raises for c in s.cases]
+
+
+def any_order(plan):
+    """rounding counts of a float32 implementation that sums in any order (what the float32 oracle, i.e. torch, is judged with):
+    tests/test_ref64_yaapt.py's ANY_ORDER with the frame-mean counts taken from the plan instead of the 400 samples of OPTS"""
+    import ref64_yaapt as r64
+    return r64.Roundings(cmul=3.25, hyp=4, nl_sum=lambda n: n, en_mean=lambda n: n, sp_mean=lambda n: n + 1, shc_sum=lambda n: n,
+                         shc_avg=lambda n: n, fm_head=lambda n: plan.tda_len + 1, fm_tail=lambda n: plan.tda_len,
+                         dot=lambda n: n + 1, pw=lambda n: n + 1)
