@@ -23,6 +23,7 @@
  * segment columns only and write segment columns only (sat_instnorm_segments_f32 aside, which owns its gaps).
  *
  * ARITHMETIC.  Exact f32, wave64, no atomics.  Each kernel is the segment form of a row kernel of sa-toolkit_amd/csrc/xvector.hip and
+ * runs that kernel's own body (csrc/xvector_tile.h, csrc/xvector_chain_body.h: one copy, shared by both), so it
  * keeps that kernel's order of operations per row — for the reductions the lane-strided loop t = lane, lane + 64, ... < T_i and the same
  * butterfly; for the chain the same (tap, input channel) order of its 96 MFMA steps — so that its result on segment i has the bits of the
  * row kernel's on utterance i alone.

@@ -24,8 +24,8 @@
  * output depends on a gap column or on another segment, NaN and infinity included.  Only segment columns of an output are written.
  *
  * ARITHMETIC.  Exact f32, wave64, no atomics, one fixed summation order.  Each kernel is the segment form of a kernel of
- * sa-toolkit_amd/csrc/conv2d.hip (the SE squeeze: of row_mean_rows_kernel, csrc/xvector.hip) and keeps its order of operations, so that
- * its result on segment i has the bits of that kernel's on utterance i alone.
+ * sa-toolkit_amd/csrc/conv2d.hip (the SE squeeze: of row_mean_rows_kernel, csrc/xvector.hip, on row_mean_wave of csrc/xvector_tile.h)
+ * and keeps its order of operations, so that its result on segment i has the bits of that kernel's on utterance i alone.
  *
  * The split-f16 form of the block convolutions on the same tables (the segment form of satools_hip_conv2d16.h's kernel, with one
  * overflow flag per segment) is declared in satools_hip_ragged2d16.h.

@@ -3,9 +3,9 @@
 // columns off_i .. off_i + T_i - 1 of every row, gap columns between them that hold anything; one table per time resolution).  The convs and
 // the pooling run the per-call kernels' own bodies (csrc/conv2d_tile.h) on each segment, the other two keep the order of operations of the
 // kernel they come from, so that segment i of a result has the bits of the per-call kernel's result on utterance i alone; each selects on
-// load (a gap column or another segment never reaches an output, NaN included) and skips what a wrong table names (segments.h).
+// load (a gap column or another segment never reaches an output, NaN included) and skips what a wrong table names (csrc/segments.h).
 #include "../conv2d_tile.h"
-#include "segments.h"
+#include "../segments.h"
 #include "../../../include/satools_hip_ragged2d.h"
 
 namespace sat {

@@ -3,9 +3,9 @@
 // one image [C][H][T_tot], time innermost, segment i at columns off_i .. off_i + T_i - 1 of every row, gap columns that hold anything).
 // The kernel runs the per-call kernel's tile body (csrc/conv2d16_tile.h) on each segment, so that segment i of its result has the bits of
 // sat_conv2d_f16x3_f32 on utterance i alone; the body selects on load (a gap column or another segment never reaches an output or an
-// overflow flag, NaN included), and the kernel skips what a wrong table names (csrc/ragged2d/segments.h).
+// overflow flag, NaN included), and the kernel skips what a wrong table names (csrc/segments.h).
 #include "../conv2d16_tile.h"
-#include "../ragged2d/segments.h"
+#include "../segments.h"
 #include "../../../include/satools_hip_ragged2d16.h"
 
 namespace sat {

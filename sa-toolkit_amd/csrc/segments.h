@@ -1,5 +1,5 @@
-// The table lookups of the segment kernels on a packed time axis (include/satools_hip_ragged2d.h), with their range checks: shared by
-// csrc/ragged2d/ and csrc/ragged2d16/.
+// The table lookups of the segment kernels on a packed time axis (include/satools_hip_ragged.h, satools_hip_ragged2d.h), with their range
+// checks: shared by csrc/ragged/, csrc/ragged2d/ and csrc/ragged2d16/.
 #pragma once
 
 namespace sat {

@@ -11,6 +11,7 @@ L2-normalised 192-dim embedding — computed on the HIP kernels:
   head        Linear(3072 -> 192) + BatchNorm on the conv kernel, L2 norm      l2norm_rows_kernel
   ragged      `extract_batch`: utterances of unequal length on one packed     csrc/ragged/xvector_ragged.hip, the segment forms of
               time axis, the convs unchanged                                   the front end, norm, chain, SE mean / gate, pooling
+  (the bodies the row and the segment kernels share: csrc/xvector_tile.h, csrc/xvector_chain_body.h)
 
 The parameter tree carries the reference's state-dict keys (torchaudio's `MelSpec.spectrogram.window` /
 `mel_scale.fb` buffers included), so a reference checkpoint loads with `load_state_dict`.  No CPU fallback."""

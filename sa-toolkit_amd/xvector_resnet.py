@@ -3,7 +3,7 @@
 `model(wav)` returns `((loss, logits), x_vector)` like the reference's forward with `target=None` — loss = NaN, logits = None, the
 L2-normalised 256-dim embedding — computed on the HIP kernels:
 
-  front end   the ECAPA net's (xvector.py): log-mel + InstanceNorm                    csrc/xvector.hip
+  front end   the ECAPA net's (xvector.py): log-mel + InstanceNorm                    csrc/xvector.hip, bodies in csrc/xvector_tile.h
   ResNet      37 Conv2d + BatchNorm2d(eval) (+ ReLU): exact f32 MFMA implicit GEMM      csrc/conv2d.hip  conv2d_mfma_kernel, conv2d_stem_kernel
               opt-in (`conv2d_precision = "f16x3"`): the 36 convs of the blocks in        csrc/conv2d16/   conv2d_f16x3_kernel
               split-f16 arithmetic, exact f32 again for a batch that leaves the f16 range

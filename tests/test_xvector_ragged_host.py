@@ -238,23 +238,33 @@ def test_the_ragged_dispatch_family_list_is_the_one_in_the_sources():
 
 
 def test_the_gpu_tests_shapes_straddle_the_wave_and_the_chains_centres():
-    text = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged", "xvector_ragged.hip")).read()
-    # the reductions stride by the 64 lanes of a wave
-    assert len(re.findall(r"t \+= 64\)", text)) >= 9 and hr.WAVE == 64
+    csrc = os.path.join(ROOT, "sa-toolkit_amd", "csrc")
+    text = open(os.path.join(csrc, "ragged", "xvector_ragged.hip")).read()      # the segment kernels: lookups, exits, pointers
+    rows = open(os.path.join(csrc, "xvector.hip")).read()                         # the row kernels
+    tile = open(os.path.join(csrc, "xvector_tile.h")).read()                      # the bodies and constants both share
+    body = open(os.path.join(csrc, "xvector_chain_body.h")).read()                # the chain's statements, included by both
+    # the reductions stride by the 64 lanes of a wave: seven loops over t in the shared row bodies (three of InstanceNorm, one of the row
+    # mean, three of the attentive statistics), two in the gap zeroing of instnorm_segments_kernel, none with another stride anywhere
+    assert [len(re.findall(r"t \+= 64\)", s)) for s in (tile, text, rows, body)] == [7, 2, 0, 0] and hr.WAVE == 64
+    assert not re.findall(r"\bt \+= (?!64\))", tile + text + rows + body)
     assert {hr.WAVE - 1, hr.WAVE, hr.WAVE + 1, 2 * hr.WAVE - 1, 2 * hr.WAVE, 2 * hr.WAVE + 1} <= set(hr.FRAMES)
     assert sorted(hr.FRAMES) == [4, 63, 64, 65, 127, 128, 129, 257] and list(hr.FRAMES) != sorted(hr.FRAMES)
     # the chain's centres: W - 2 HALO columns of a window of 64 NT, NT = 2 and 3
-    halo = int(re.search(r"constexpr int RG_MARG = \d+, RG_HALO = (\d+);", text).group(1))
-    assert "TT = W - 2 * RG_HALO" in text and "constexpr int W = 64 * NT" in text
+    halo = int(re.search(r"constexpr int R2_MARG = \d+, R2_HALO = (\d+);", tile).group(1))
+    assert "TT = W - 2 * R2_HALO" in body and "constexpr int W = 64 * NT" in body
+    assert text.count('#include "../xvector_chain_body.h"') == 1 and rows.count('#include "xvector_chain_body.h"') == 1
     centres = sorted(64 * nt - 2 * halo for nt in (2, 3))
-    assert "launch_res2_chain_segments<2>" in text and "launch_res2_chain_segments<3>" in text and centres == sorted(hr.CENTRES) == [64, 128]
+    for src, kernel in ((text, "res2_chain_segments_kernel"), (rows, "res2_chain_kernel")):
+        assert f"launch_res2_chain<2>({kernel}<2>," in src and f"launch_res2_chain<3>({kernel}<3>," in src
+    assert centres == sorted(hr.CENTRES) == [64, 128]
     # one below / at / one above the 64-column centre; at / one above the 128-column centre (127 is not among the lengths: 65 ends inside its first
     # tile like 127 would); 193 = one column into a fourth 64-column and a second 128-column tile; 7 < the halo
     assert {63, 64, 65} <= set(hr.CHAIN_FRAMES) and {128, 129} <= set(hr.CHAIN_FRAMES) and 193 == 3 * 64 + 1 and min(hr.CHAIN_FRAMES) < halo
     assert sorted(hr.CHAIN_FRAMES) == [7, 63, 64, 65, 128, 129, 193] and set(hr.CHAIN_CASES) == {(7, 2), (7, 3), (7, 4), (3, 1)}
     assert all(n * d <= halo for n, d in hr.CHAIN_CASES)
     # the front end: frames = 1 + n // 160, four frames per block, 513 samples the shortest
-    assert int(re.search(r"constexpr int RG_FPB = (\d+);", text).group(1)) == 4 and int(re.search(r"constexpr int RG_HOP = (\d+);", text).group(1)) == ops.XV_HOP
+    assert int(re.search(r"constexpr int XV_FPB = (\d+);", tile).group(1)) == 4 and int(re.search(r"constexpr int XV_HOP = (\d+);", tile).group(1)) == ops.XV_HOP
+    assert "ceil_div(1 + n_max / XV_HOP, XV_FPB)" in text and "ceil_div(frames, XV_FPB)" in rows          # both grids are sized by them
     assert sorted(1 + n // ops.XV_HOP for n in hr.FRONT_SAMPLES) == [4, 5, 63, 64, 65, 151] and min(hr.FRONT_SAMPLES) == ops.XV_MIN_SAMPLES
     assert sorted(hr.NET_SAMPLES) == [641, 8000, 10079, 10080, 16000, 24123]
     # every channel count leaves a block of four waves ending inside a row of segments, and the gate kernel's channel group is straddled
