@@ -358,7 +358,7 @@ class _TdnnfBase(nn.Module):
 
     def _tdnnf_layer(self, lay, c, x, xs=None, return_bottleneck=False, want_aux=False, row_frames=None, tie=None, skip_f32=False, x_valid=True):
         """x [B, feat, T] -> [B, out, T'] (or the bottleneck [B, bott, T']).  In split-f16 mode the layers
-        hand their activations on as split planes as well (`xs`, csrc/conv1d_mfma.hip): linearB then
+        hand their activations on as split planes as well (`xs`, csrc/conv_f16x3.hip): linearB then
         stages its 1024 x 3 input with 16-byte copies and linearA reads the bottleneck from planes; the
         f32 tensor stays for the bypass connection.  Returns (y, planes of y or None).
         skip_f32: the f32 output is not stored (y is then an unwritten shape carrier: the successor takes the planes); x_valid = False:

@@ -126,6 +126,39 @@ int g_stamp_variant = 0;   // 1: no output stores, 2: no residual, 3: neither
 #define SAT_STAMP_BLOCK(i, expr)
 #endif
 
+// ---- pieces of the split-f16 kernels on 32x32x16 tiles (conv_f16x3.hip, pair.hip, act_split.hip) ----
+// acc += a x b with both operands carried as hi + lo f16: lo.hi, then hi.lo, then hi.hi.  f32 accumulation rounds after
+// every MFMA, so this ORDER (the small terms first) is what fixes the result bits: it is written here and nowhere else.
+__device__ __forceinline__ void mfma_split3(f32x16& acc, const h8& a_hi, const h8& a_lo, const h8& b_hi, const h8& b_lo) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc, 0, 0, 0);
+}
+
+// two f32 -> their packed f16 pairs hi = rtz(x) and lo = rtz(x - hi) (the subtraction in f32; split_lo2 of common.h is the
+// v_fma_mix form of the same bits)
+__device__ __forceinline__ void split_hilo2(float x0, float x1, unsigned& hi, unsigned& lo) {
+  const auto h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
+  const auto l = __builtin_amdgcn_cvt_pkrtz(x0 - (float)h[0], x1 - (float)h[1]);
+  hi = __builtin_bit_cast(unsigned, h);
+  lo = __builtin_bit_cast(unsigned, l);
+}
+// eight channels at one position -> the hi and the lo 16-byte unit of a split plane, a leaky-ReLU applied first if `act`
+__device__ __forceinline__ void split_hilo8(const float (&x)[8], bool act, float slope, uint4& hi, uint4& lo) {
+  unsigned h[4], l[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float x0 = x[2 * j], x1 = x[2 * j + 1];
+    if (act) {
+      x0 = lrelu_max(x0, slope);
+      x1 = lrelu_max(x1, slope);
+    }
+    split_hilo2(x0, x1, h[j], l[j]);
+  }
+  hi = make_uint4(h[0], h[1], h[2], h[3]);
+  lo = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
 // ---- epilogue shared by the exact-f32 and the split-f16 kernels: bias, residual / bypass, folded
 // BatchNorm, ReLU, MRF accumulation, (polyphase) store ----
 // residual of the whole wave tile fetched ahead of the epilogue (fast path only): issued before the last
@@ -656,6 +689,26 @@ inline bool epilogue16_supports(const ConvArgs& a) {
   return a.fast_epi && !a.y16_f8 && a.up == 1 && !a.poly_planes && a.rows_g % 4 == 0;
 }
 
+// launch of 256-thread blocks, the kernel's dynamic-LDS limit raised first where it needs more than 64 KB; the launcher's own
+// SAT_LAUNCH_CHECK follows (it records the launcher's signature)
+template <class Kernel>
+inline int launch_lds(Kernel kern, dim3 grid, size_t lds_bytes, hipStream_t s, const ConvArgs& p) {
+  if (lds_bytes > 64 * 1024) SAT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, p);
+  return SAT_OK;
+}
+
+// exact-f32 conv, the tile shape chosen by rows and blocks (conv1d_mfma.hip)
+int launch_conv1d_f32(const ConvArgs& a, int B, int groups, hipStream_t s);
+// split-f16 conv on 32x32 MFMA tiles (conv_f16x3.hip): 64 rows x 128 positions (3 or 7 taps), 64 x 256, 32 x 512
+int launch_f16x3_64x128(const ConvArgs& a, int B, int groups, hipStream_t s);
+int launch_f16x3_64x256(const ConvArgs& a, int B, int groups, hipStream_t s);
+int launch_f16x3_32x512(const ConvArgs& a, int B, int groups, hipStream_t s);
+int launch_f16x3_k1(const ConvArgs& a, int B, hipStream_t s);   // 1x1 on split planes, 128 x 128 tiles, activations straight from the planes
+// fused ResBlock1 step (pair.hip): C <= 32 from f32 or planes; C = 16 and C = 32 with split planes end to end
+int launch_pair(const ConvArgs& a, int B, hipStream_t s);
+int launch_pair16(const ConvArgs& a, int B, hipStream_t s);
+int launch_pair32(const ConvArgs& a, int B, hipStream_t s);   // a.xw = the staged columns conv1 reads
 // 1x1 convolution on split planes through the LDS-DMA ring GEMM (gemm_ring.hip)
 int launch_f16x3_ring(const ConvArgs& a, int B, hipStream_t s);
 // fused ResBlock1 step for C = 64, 3 taps (pair64.hip)

@@ -15,7 +15,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv1d_f16x3_planes_kernel (conv1d_mfma.hip) holds 235 VGPRs — two fragment sets and 64 residual-prefetch registers —
+// conv1d_f16x3_planes_kernel (conv_f16x3.hip) holds 235 VGPRs — two fragment sets and 64 residual-prefetch registers —
 // and up to 65 KB of LDS: two blocks per CU, and its launches wait on memory 14-35 % of their cycles.  This form trades
 // the deeper per-wave pipelining for a third co-resident block: one flowing fragment set, the residual loaded in the
 // epilogue, the folded-BatchNorm step compiled out (<= 168 VGPRs), and for 11 taps the weights of a chunk pass through

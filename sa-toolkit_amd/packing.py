@@ -142,7 +142,7 @@ def move_packed(w: torch.Tensor, *args, **kwargs) -> torch.Tensor:
     return out
 
 
-F8_W_HI_EXP, F8_W_LO_EXP, F8_X_LO_EXP = 6, 16, 10      # power-of-two scales of the e4m3 operands (csrc/conv1d_mfma.hip)
+F8_W_HI_EXP, F8_W_LO_EXP, F8_X_LO_EXP = 6, 16, 10      # power-of-two scales of the e4m3 operands (csrc/conv_common.h)
 
 
 def pack_conv_weight_f16f8(w: torch.Tensor, groups: int = 1, up: int = 1) -> torch.Tensor:

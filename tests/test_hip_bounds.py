@@ -1068,8 +1068,8 @@ def _(B, Cc, T):
     return c
 
 
-# ---- the fused 1-D convolution in every arithmetic and layout it dispatches (csrc/conv1d_mfma.hip, conv_lean.hip, conv_ring16.hip,
-# gemm_ring.hip, gemm_walk16.hip) -----------------------------------------------------------------------------------------------
+# ---- the fused 1-D convolution in every arithmetic and layout it dispatches (csrc/conv1d_api.hip: conv1d_mfma.hip, conv_f16x3.hip, conv_lean.hip,
+# conv_ring16.hip, gemm_ring.hip, gemm_walk16.hip) ------------------------------------------------------------------------------
 def _pack(w, mode, **kw):
     """packed weights (on the device, as the product packs them) and the attributes that travel with the tensor"""
     _, _, packing = _sat()
@@ -1473,7 +1473,7 @@ def _(B, ctx, feat, bott, out, T, how, bypass):
     return c
 
 
-# ---- fused ResBlock steps, the MRF block, the thin upsamplers (conv1d_mfma.hip, pair32s.hip, pair64.hip, mrf.hip, ups2.hip) -----------
+# ---- fused ResBlock steps, the MRF block, the thin upsamplers (pair.hip, pair32s.hip, pair64.hip, mrf.hip, ups2.hip) -----------
 def pair_rows(name, tile, family, Cc, k, dil, *, planes, scaled=True, no_y=False, accum=False, options=(), bound=2e-5, extra=()):
     """out = conv2(lrelu(conv1(lrelu(x)) + b1)) + b2 + x.  `bound`: 2e-5 for the general fused steps (tests/test_hip_parity.py::
     test_fused_resblock_pair_matches_torch), 1e-5 for the streaming ones and C = 64 (::test_streaming_resblock_step_matches_the_general_fused_step)"""

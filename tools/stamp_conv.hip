@@ -8,7 +8,8 @@
 #include <vector>
 
 #include "../sa-toolkit_amd/csrc/api.hip"
-#include "../sa-toolkit_amd/csrc/conv1d_mfma.hip"
+#include "../sa-toolkit_amd/csrc/conv_f16x3.hip"
+#include "../sa-toolkit_amd/csrc/conv1d_api.hip"
 
 #define CK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
