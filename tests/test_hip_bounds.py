@@ -73,6 +73,7 @@ class Case:
     family: str = None
     options: tuple = ()          # (name, value, default) of sat_conv_set_option for the duration of the case
     tol: float = None            # entry points with floating-point atomics only (none)
+    data: dict = field(default_factory=dict)          # the generated inputs by name (tests/test_hip_tile_walk.py cuts sub-batches and crops out of them)
 
     def _add(self, name, role, shape=None, dtype=torch.float32, data=None, **kw):
         if data is not None:
@@ -1091,7 +1092,7 @@ def _lrelu(v, slope):
 
 def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=1, x_planes=False, slope=None, y_planes=False, no_y=False, sidecar=False,
               hi_only=False, res=None, res_toff=0, res_tstride=1, res_scale=1.0, post_res=False, accum=False, accum_div=0.0, affine=False, relu=False,
-              gelu=False, ypitch=0, wrap=0, family=None, options=(), bound=3e-5):
+              gelu=False, ypitch=0, wrap=0, family=None, options=(), bound=3e-5, x=None):
     """one sat_conv1d_f32 call.  `bound`: 3e-5 absolute on these O(1) outputs, the bar of tests/test_hip_parity.py::test_conv1d_matches_torch and
     ::test_conv1d_split_f16_matches_torch (exact f32 and split-f16 alike); SAT_CONV_F16F8R: 1e-4 of the scale, tests/test_hip_f8r.py"""
     _, ops, _ = _sat()
@@ -1100,7 +1101,8 @@ def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=
     pl, pr = pads if pads is not None else (halo // 2, halo - halo // 2)
     cx = wrap or cin
     T_q = T if wrap else (T + pl + pr - halo - 1) // stride + 1
-    x = rand(B, cx, T, seed=T + cin)
+    x = rand(B, cx, T, seed=T + cin) if x is None else x          # (`x`: a given input, a sub-batch of another case's)
+    c.data["x"] = x
     w = rand(cout, cin // groups, k, seed=2, scale=(cin // groups * k) ** -0.5)
     b = rand(cout, seed=3)
     wp, attrs = _pack(w, mode, **({"groups": groups} if mode != 3 else {}))
@@ -1335,8 +1337,8 @@ ups_rows("planes up_grouped all taps sidecar", 160, "conv1d_f16x3_ring16_kernel"
 
 
 # ---- several convs in one call ---------------------------------------------------------------------------------------------------
-@row("sat_conv1d_multi_f32", "three ring jobs chained through the MRF sum", [(1, 1), (3, 319), (1, 320), (3, 321), (3, 677)])
-def _(B, T):
+def multi_ring_case(B, T):
+    """three ring jobs of one launch chained through the MRF sum (index order inside a block: no rotation)"""
     _, ops, _ = _sat()
     Cc, ks, dils = 128, (3, 7, 11), (1, 3, 5)
     c = Case(family="conv1d_f16x3_ring16_kernel", options=RING)
@@ -1372,6 +1374,9 @@ def _(B, T):
         assert torch.equal(t["y_split"], ops.act_split(t["acc"].contiguous(), 0.1))
     c.ref = ref
     return c
+
+
+row("sat_conv1d_multi_f32", "three ring jobs chained through the MRF sum", [(1, 1), (3, 319), (1, 320), (3, 321), (3, 677)])(multi_ring_case)
 
 
 @row("sat_conv1d_multi_f32", "q | k | v on the persistent GEMM", [(1, 255), (3, 256), (3, 677)])
@@ -1474,71 +1479,76 @@ def _(B, ctx, feat, bott, out, T, how, bypass):
 
 
 # ---- fused ResBlock steps, the MRF block, the thin upsamplers (pair.hip, pair32s.hip, pair64.hip, mrf.hip, ups2.hip) -----------
-def pair_rows(name, tile, family, Cc, k, dil, *, planes, scaled=True, no_y=False, accum=False, options=(), bound=2e-5, extra=()):
+def pair_case(B, T, Cc, k, dil, *, planes, scaled=True, no_y=False, accum=False, family=None, options=(), bound=2e-5, x=None, acc0=None):
     """out = conv2(lrelu(conv1(lrelu(x)) + b1)) + b2 + x.  `bound`: 2e-5 for the general fused steps (tests/test_hip_parity.py::
-    test_fused_resblock_pair_matches_torch), 1e-5 for the streaming ones and C = 64 (::test_streaming_resblock_step_matches_the_general_fused_step)"""
+    test_fused_resblock_pair_matches_torch), 1e-5 for the streaming ones and C = 64 (::test_streaming_resblock_step_matches_the_general_fused_step).
+    `x`, `acc0`: a given input and accumulator (a sub-batch or a crop of another case's) in place of the seeded ones"""
     entry = "sat_resblock_pair_scaled_f16x3" if scaled else "sat_resblock_pair_f16x3"
+    lib, ops, packing = _sat()
+    c = Case(family=family, options=tuple(options))
+    x = rand(B, Cc, T, seed=T + Cc) if x is None else x
+    w1, w2 = rand(Cc, Cc, k, seed=2, scale=0.6 / np.sqrt(Cc * k)), rand(Cc, Cc, k, seed=3, scale=0.6 / np.sqrt(Cc * k))
+    b1, b2 = rand(Cc, seed=4, scale=0.1), rand(Cc, seed=5, scale=0.1)
+    acc0 = rand(B, Cc, T, seed=6) if acc0 is None else acc0
+    c.data.update(x=x, acc0=acc0)
+    p1, p2 = (packing.pack_conv_weight_f16x3(w.to(DEV), scale=scaled) for w in (w1, w2))
+    xs = ops.act_split(x.to(DEV), 0.1) if planes else None
+    if planes:
+        c.inp("x_split", xs)
+        c.out("y_split", (B, Cc // 16, 2, 2, T, 8), F16)
+    else:
+        c.inp("x", x)
+    for n, v in (("w1", p1), ("w2", p2), ("b1", b1), ("b2", b2)):
+        c.inp(n, v)
+    if no_y:
+        c.untouched("y", (B, Cc, T))
+    elif accum:
+        c.inout("y", acc0)
+    else:
+        c.out("y", (B, Cc, T))
 
-    @row(entry, name, times(tile) + list(extra))
-    def _(B, T):
-        lib, ops, packing = _sat()
-        c = Case(family=family, options=tuple(options))
-        x = rand(B, Cc, T, seed=T + Cc)
-        w1, w2 = rand(Cc, Cc, k, seed=2, scale=0.6 / np.sqrt(Cc * k)), rand(Cc, Cc, k, seed=3, scale=0.6 / np.sqrt(Cc * k))
-        b1, b2 = rand(Cc, seed=4, scale=0.1), rand(Cc, seed=5, scale=0.1)
-        acc0 = rand(B, Cc, T, seed=6)
-        p1, p2 = (packing.pack_conv_weight_f16x3(w.to(DEV), scale=scaled) for w in (w1, w2))
-        xs = ops.act_split(x.to(DEV), 0.1) if planes else None
+    def call(t):
+        d = lib.ConvDesc()
+        d.B, d.C_in, d.T_in, d.C_out, d.T_q = B, Cc, T, Cc, T
+        d.ksize, d.dilation, d.stride, d.pad_left, d.groups, d.up, d.mode = k, dil, 1, 0, 1, 1, 1
+        d.in_lrelu, d.in_slope = 1, 0.1
+        d.accum, d.accum_div = int(accum), 3.0 if accum else 0.0
+        d.res_scale, d.res_toff, d.res_tstride = 1.0, 0, 1
+        d.x_bstride = d.y_bstride = d.res_bstride = Cc * T
+        d.x_cstride = d.y_cstride = d.res_cstride = T
+        d.bias, d.res = P(t["b2"]), P(t.get("x"))
+        d.x_split, d.y_split, d.y_split_slope = P(t.get("x_split")), P(t.get("y_split")), 0.1
         if planes:
-            c.inp("x_split", xs)
-            c.out("y_split", (B, Cc // 16, 2, 2, T, 8), F16)
+            d.res_split, d.res_split_slope = P(t["x_split"]), 0.1
+        d.no_y = int(no_y)
+        d.w_descale = p2.w_descale
+        if scaled:
+            _ok(_L().sat_resblock_pair_scaled_f16x3(C.byref(d), P(t.get("x")), P(t["w1"]), P(t["b1"]), p1.w_descale, P(t["w2"]), P(t["y"]), _stream()), entry)
         else:
-            c.inp("x", x)
-        for n, v in (("w1", p1), ("w2", p2), ("b1", b1), ("b2", b2)):
-            c.inp(n, v)
-        if no_y:
-            c.untouched("y", (B, Cc, T))
-        elif accum:
-            c.inout("y", acc0)
-        else:
-            c.out("y", (B, Cc, T))
+            _ok(_L().sat_resblock_pair_f16x3(C.byref(d), P(t.get("x")), P(t["w1"]), P(t["b1"]), P(t["w2"]), P(t["y"]), _stream()), entry)
+    c.call = call
 
-        def call(t):
-            d = lib.ConvDesc()
-            d.B, d.C_in, d.T_in, d.C_out, d.T_q = B, Cc, T, Cc, T
-            d.ksize, d.dilation, d.stride, d.pad_left, d.groups, d.up, d.mode = k, dil, 1, 0, 1, 1, 1
-            d.in_lrelu, d.in_slope = 1, 0.1
-            d.accum, d.accum_div = int(accum), 3.0 if accum else 0.0
-            d.res_scale, d.res_toff, d.res_tstride = 1.0, 0, 1
-            d.x_bstride = d.y_bstride = d.res_bstride = Cc * T
-            d.x_cstride = d.y_cstride = d.res_cstride = T
-            d.bias, d.res = P(t["b2"]), P(t.get("x"))
-            d.x_split, d.y_split, d.y_split_slope = P(t.get("x_split")), P(t.get("y_split")), 0.1
-            if planes:
-                d.res_split, d.res_split_slope = P(t["x_split"]), 0.1
-            d.no_y = int(no_y)
-            d.w_descale = p2.w_descale
-            if scaled:
-                _ok(_L().sat_resblock_pair_scaled_f16x3(C.byref(d), P(t.get("x")), P(t["w1"]), P(t["b1"]), p1.w_descale, P(t["w2"]), P(t["y"]), _stream()), entry)
-            else:
-                _ok(_L().sat_resblock_pair_f16x3(C.byref(d), P(t.get("x")), P(t["w1"]), P(t["b1"]), P(t["w2"]), P(t["y"]), _stream()), entry)
-        c.call = call
-
-        def ref(t):
-            xd = x.double()
-            t1 = F.conv1d(F.leaky_relu(xd, 0.1), w1.double(), b1.double(), dilation=dil, padding=(k * dil - dil) // 2)
-            v = F.conv1d(F.leaky_relu(t1, 0.1), w2.double(), b2.double(), padding=(k - 1) // 2) + xd
-            if accum:
-                v = (acc0.double() + v) / 3
+    def ref(t):
+        xd = x.double()
+        t1 = F.conv1d(F.leaky_relu(xd, 0.1), w1.double(), b1.double(), dilation=dil, padding=(k * dil - dil) // 2)
+        v = F.conv1d(F.leaky_relu(t1, 0.1), w2.double(), b2.double(), padding=(k - 1) // 2) + xd
+        if accum:
+            v = (acc0.double() + v) / 3
+        if not no_y:
+            bounded("resblock_pair y", t["y"], v, bound)
+        if planes:
+            want = F.leaky_relu(v, 0.1)
+            bounded("resblock_pair y_split", ops.unsplit(t["y_split"]), want, bound + 2.0 ** -21 * want.abs())
             if not no_y:
-                bounded("resblock_pair y", t["y"], v, bound)
-            if planes:
-                want = F.leaky_relu(v, 0.1)
-                bounded("resblock_pair y_split", ops.unsplit(t["y_split"]), want, bound + 2.0 ** -21 * want.abs())
-                if not no_y:
-                    assert torch.equal(t["y_split"], ops.act_split(t["y"].contiguous(), 0.1))
-        c.ref = ref
-        return c
+                assert torch.equal(t["y_split"], ops.act_split(t["y"].contiguous(), 0.1))
+    c.ref = ref
+    return c
+
+
+def pair_rows(name, tile, family, Cc, k, dil, *, scaled=True, extra=(), **kw):
+    @row("sat_resblock_pair_scaled_f16x3" if scaled else "sat_resblock_pair_f16x3", name, times(tile) + list(extra))
+    def _(B, T):
+        return pair_case(B, T, Cc, k, dil, scaled=scaled, family=family, **kw)
 
 
 pair_rows("C16 f32-in k3", 224, "resblock_pair_f16x3_kernel", 16, 3, 1, planes=False)
@@ -1565,12 +1575,13 @@ def _mrf_weights(Cc, ks, seed):
     return steps
 
 
-@row("sat_resblock_mrf_f16x3", "C16 block", [(b, t, 3, 1) for b, t in times(512)] + [(3, 60, 3, 0), (1, 11, 1, 1), (3, 513, 1, 0)])
-def _(B, T, nb, rfp):
+def mrf_case(B, T, nb=3, rfp=1, x=None):
+    """the C = 16 MRF block in one launch; `x`: a given input in place of the seeded one"""
     lib, ops, packing = _sat()
     Cc = 16
     c = Case(family="mrf16_kernel")
-    x = rand(B, Cc, T, seed=T)
+    x = rand(B, Cc, T, seed=T) if x is None else x
+    c.data["x"] = x
     xs = ops.act_split(x.to(DEV), 0.1)
     branches = [(3, _mrf_weights(Cc, 3, 100)), (7, _mrf_weights(Cc, 7, 200)), (11, _mrf_weights(Cc, 11, 300))][:nb] if nb == 3 else [(7, _mrf_weights(Cc, 7, 200))]
     desc = {}
@@ -1624,27 +1635,36 @@ def _(B, T, nb, rfp):
     return c
 
 
+row("sat_resblock_mrf_f16x3", "C16 block", [(b, t, 3, 1) for b, t in times(512)] + [(3, 60, 3, 0), (1, 11, 1, 1), (3, 513, 1, 0)])(mrf_case)
+
+
+def ups2_case(B, T, cin, x=None):
+    """the thin stride-2 upsampler; `x`: a given input in place of the seeded one"""
+    _, ops, packing = _sat()
+    c = Case(family="ups2_kernel")
+    cout = cin // 2
+    x = rand(B, cin, T, seed=T + cin) if x is None else x
+    c.data["x"] = x
+    w, b = rand(cin, cout, 4, seed=2, scale=0.8 / np.sqrt(cin * 2)), rand(cout, seed=3, scale=0.1)
+    wc, kp, pl = packing.convtranspose_as_phase_conv(w.to(DEV), 2, 1)
+    wp = packing.pack_conv_weight_f16x3(wc, up=2)
+    c.inp("x_split", ops.act_split(x.to(DEV), 0.1))
+    c.inp("w", wp)
+    c.inp("bias", b)
+    c.out("y_split", (B, cout // 16, 2, 2, 2 * T, 8), F16)
+    c.call = lambda t: ops.upsample2(t["x_split"], _attrs(t["w"], {"w_descale": wp.w_descale}), t["bias"], B, cin, T, y_split_slope=0.1, y_split=t["y_split"])
+
+    def ref(t):      # tests/test_hip_parity.py::test_streaming_upsampler_matches_the_polyphase_conv_and_torch: 1e-5
+        want = F.leaky_relu(F.conv_transpose1d(F.leaky_relu(x.double(), 0.1), w.double(), b.double(), stride=2, padding=1), 0.1)
+        bounded("upsample2", ops.unsplit(t["y_split"]), want, 1e-5)
+    c.ref = ref
+    return c
+
+
 def ups2_rows(cin, tile):
     @row("sat_upsample2_f16x3", f"C{cin}", times(tile))
     def _(B, T):
-        _, ops, packing = _sat()
-        c = Case(family="ups2_kernel")
-        cout = cin // 2
-        x = rand(B, cin, T, seed=T + cin)
-        w, b = rand(cin, cout, 4, seed=2, scale=0.8 / np.sqrt(cin * 2)), rand(cout, seed=3, scale=0.1)
-        wc, kp, pl = packing.convtranspose_as_phase_conv(w.to(DEV), 2, 1)
-        wp = packing.pack_conv_weight_f16x3(wc, up=2)
-        c.inp("x_split", ops.act_split(x.to(DEV), 0.1))
-        c.inp("w", wp)
-        c.inp("bias", b)
-        c.out("y_split", (B, cout // 16, 2, 2, 2 * T, 8), F16)
-        c.call = lambda t: ops.upsample2(t["x_split"], _attrs(t["w"], {"w_descale": wp.w_descale}), t["bias"], B, cin, T, y_split_slope=0.1, y_split=t["y_split"])
-
-        def ref(t):      # tests/test_hip_parity.py::test_streaming_upsampler_matches_the_polyphase_conv_and_torch: 1e-5
-            want = F.leaky_relu(F.conv_transpose1d(F.leaky_relu(x.double(), 0.1), w.double(), b.double(), stride=2, padding=1), 0.1)
-            bounded("upsample2", ops.unsplit(t["y_split"]), want, 1e-5)
-        c.ref = ref
-        return c
+        return ups2_case(B, T, cin)
 
 
 ups2_rows(32, 496)
