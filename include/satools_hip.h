@@ -161,7 +161,8 @@ typedef struct {
   int32_t no_y;            /* skip the f32 store of y (y may be NULL) */
   const void* res_split;   /* residual taken from SAT_SPLIT_F16 planes of lrelu(r, res_split_slope) instead of `res`
                               (r = hi + lo, the leaky-relu undone on the fly: 22 significand bits of r); with it
-                              a chain of layers needs no f32 copy of its activations.  up 1, groups 1 */
+                              a chain of layers needs no f32 copy of its activations.  up 1, groups 1, C_out % 16 == 0; a
+                              split-f16 mode (SAT_CONV_F32 refuses it like every other split-plane field) */
   float res_split_slope;
   int32_t y_split_format;  /* 0 = the format this mode reads (F16X3: SAT_SPLIT_F16, F16F8: SAT_SPLIT_F8),
                               1 = SAT_SPLIT_F16, 2 = SAT_SPLIT_F8 */

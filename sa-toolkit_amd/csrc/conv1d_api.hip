@@ -117,7 +117,8 @@ static int conv1d_prepare(const sat_conv1d_desc* d, const float* x, const void* 
     const long long rlim = d->res ? ((long long)a.rows_g * a.r_cs + (long long)a.T_q * a.res_tstride + a.res_toff) * 4 : 0;
     a.fast_epi = d->up == 1 && ylim < (1LL << 31) && rlim < (1LL << 31) && ylim > 0;
   }
-  SAT_REQUIRE(d->mode != SAT_CONV_F32 || (!d->x_split && !d->y_split && !d->no_y), "conv1d: split planes need a split-f16 mode");
+  // (res_split among them: the exact-f32 kernels never look at it, and a descriptor that names a residual must not run without one)
+  SAT_REQUIRE(d->mode != SAT_CONV_F32 || (!d->x_split && !d->y_split && !d->no_y && !d->res_split), "conv1d: split planes need a split-f16 mode");
   if (d->mode == SAT_CONV_F16X3 || d->mode == SAT_CONV_F16F8 || d->mode == SAT_CONV_F16F8R) {
     a.f8 = d->mode == SAT_CONV_F16F8;
     a.f8r = d->mode == SAT_CONV_F16F8R;

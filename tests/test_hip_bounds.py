@@ -1090,9 +1090,38 @@ def _lrelu(v, slope):
     return v if slope is None else F.leaky_relu(v, slope)
 
 
+def conv_want(pre, w, b, r, sc, sh, acc0, T_q, *, cin, dil=1, stride=1, pads=(0, 0), groups=1, res_toff=0, res_tstride=1, res_scale=1.0, post_res=False, accum=False,
+              accum_div=0.0, affine=False, relu=False, gelu=False, relu_first=False, wrap=0):
+    """the float64 value conv_case holds a call to, in the order of sat_conv1d_desc's epilogue (include/satools_hip.h); pre = pre(x) in float64, r = the
+    residual or None.  No GPU: tests/test_ref64_conv.py compares it with tests/ref64_conv.py on every row of CONV_ROWS"""
+    if wrap:
+        nxt = F.pad(pre[:, :cin - wrap, 1:], (0, 1))
+        v = F.conv1d(pre, w[:, :wrap].double(), b.double()) + F.conv1d(nxt, w[:, wrap:].double())
+    else:
+        v = F.conv1d(F.pad(pre, pads), w.double(), b.double(), stride=stride, dilation=dil, groups=groups)[..., :T_q]
+    rd = None if r is None else r.double()
+    if rd is not None and not post_res:
+        v = v + res_scale * rd[:, :, res_toff::res_tstride][..., :T_q]
+    if relu and relu_first:
+        v = F.relu(v)
+    if affine:
+        v = v * sc.double()[None, :, None] + sh.double()[None, :, None]
+    if relu and not relu_first:
+        v = F.relu(v)
+    if gelu:
+        v = F.gelu(v)
+    if post_res:
+        v = v + rd
+    if accum:
+        v = acc0.double()[..., :T_q] + v
+        if accum_div:
+            v = v / accum_div
+    return v
+
+
 def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=1, x_planes=False, slope=None, y_planes=False, no_y=False, sidecar=False,
               hi_only=False, res=None, res_toff=0, res_tstride=1, res_scale=1.0, post_res=False, accum=False, accum_div=0.0, affine=False, relu=False,
-              gelu=False, ypitch=0, wrap=0, family=None, options=(), bound=3e-5, x=None):
+              gelu=False, relu_first=False, ypitch=0, wrap=0, family=None, options=(), bound=3e-5, x=None):
     """one sat_conv1d_f32 call.  `bound`: 3e-5 absolute on these O(1) outputs, the bar of tests/test_hip_parity.py::test_conv1d_matches_torch and
     ::test_conv1d_split_f16_matches_torch (exact f32 and split-f16 alike); SAT_CONV_F16F8R: 1e-4 of the scale, tests/test_hip_f8r.py"""
     _, ops, _ = _sat()
@@ -1147,7 +1176,7 @@ def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=
         kw = dict(bias=t["bias"], dilation=dil, stride=stride, pad_left=pl, pad_right=pr, groups=groups, mode=mode, out=t["y"][:, :, :T_q], accum=accum,
                   accum_div=accum_div, relu=relu, gelu=gelu, x_split=t.get("x_split"), x_split8=t.get("x_split8"), y_split=t.get("y_split"),
                   y_split8=t.get("y_split8"), y_split_hi_only=hi_only, y_split_slope=0.1, no_y=no_y, res_split=t.get("res_split"), res_split_slope=0.1,
-                  ch_scale=t.get("ch_scale"), ch_shift=t.get("ch_shift"))
+                  ch_scale=t.get("ch_scale"), ch_shift=t.get("ch_shift"), relu_first=relu_first)
         if res == "f32":
             kw.update(post_res=t["res"]) if post_res else kw.update(res=t["res"], res_scale=res_scale, res_toff=res_toff, res_tstride=res_tstride)
         if slope is not None and not x_planes:
@@ -1160,26 +1189,8 @@ def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=
     def ref(t):
         # (SAT_SPLIT_F16 planes: the 22 bits of pre(x) the kernel is given)
         pre = ops.unsplit(xs).double().cpu() if x_planes and mode != 2 else _lrelu(x.double(), slope)
-        if wrap:
-            nxt = F.pad(pre[:, :cin - wrap, 1:], (0, 1))
-            v = F.conv1d(pre, w[:, :wrap].double(), b.double()) + F.conv1d(nxt, w[:, wrap:].double())
-        else:
-            v = F.conv1d(F.pad(pre, (pl, pr)), w.double(), b.double(), stride=stride, dilation=dil, groups=groups)[..., :T_q]
-        rd = None if r is None else (r.double() if res == "f32" else r.double())
-        if rd is not None and not post_res:
-            v = v + res_scale * rd[:, :, res_toff::res_tstride][..., :T_q]
-        if affine:
-            v = v * sc.double()[None, :, None] + sh.double()[None, :, None]
-        if relu:
-            v = F.relu(v)
-        if gelu:
-            v = F.gelu(v)
-        if post_res:
-            v = v + rd
-        if accum:
-            v = acc0.double()[..., :T_q] + v
-            if accum_div:
-                v = v / accum_div
+        v = conv_want(pre, w, b, r, sc, sh, acc0, T_q, cin=cin, dil=dil, stride=stride, pads=(pl, pr), groups=groups, res_toff=res_toff, res_tstride=res_tstride,
+                      res_scale=res_scale, post_res=post_res, accum=accum, accum_div=accum_div, affine=affine, relu=relu, gelu=gelu, relu_first=relu_first, wrap=wrap)
         bd = bound * max(1.0, float(v.abs().max())) if mode == 3 else bound
         if not no_y:
             bounded("conv1d y", t["y"][:, :, :T_q], v, bd)
@@ -1207,7 +1218,11 @@ def conv_case(B, T, cin, cout, k, *, mode=0, dil=1, stride=1, pads=None, groups=
     return c
 
 
+CONV_ROWS = []          # (name, shapes, keyword arguments of conv_case) of every row conv_rows adds
+
+
 def conv_rows(name, tile, family, shapes=None, **kw):
+    CONV_ROWS.append((name, shapes or times(tile), dict(kw)))
     cin, cout, k = kw.pop("cin"), kw.pop("cout"), kw.pop("k")
 
     @row("sat_conv1d_f32", name, shapes or times(tile))
