@@ -4,7 +4,7 @@
 // the batch, forced onto the CPU) with the options of egs/vc/libritts/local/tuning/hifigan.py:31-36.
 // Kernel by kernel:
 //   prefilter     SignalObj.filtered_version :42-51 (torchaudio biquads; third-party)
-//   nlfer_frames  nlfer :148-176                    one 8192-point FFT in LDS per frame
+//   nlfer_frames  nlfer :148-176                    one 8192-point real FFT in LDS per frame (4096 packed points)
 //   energy_norm   PitchObj.set_energy :125-128
 //   spec_frames   spec_track :209-238 + peaks :383-497   FFT -> |X| -> SHC -> candidate peaks
 //   spec_post     spec_track :241-312, dynamic5 :506-523, path1 :530-570, medfilt :54-69
@@ -22,8 +22,9 @@ namespace sat {
 
 typedef sat_yaapt_plan Plan;
 
-constexpr int FFT_N = 8192;
-constexpr int FFT_LOG = 13;
+constexpr int FFT_N = 8192;          // fft_length: the real transform whose bins the stages read
+constexpr int FFT_LOG = 12;          // the frames are real: two samples per complex point, FFT_N / 2 points (see the FFT below)
+constexpr int FFT_NP = 1 << FFT_LOG;
 constexpr int MAXP = 4;   // shc_maxpeaks
 constexpr int NC = 6;     // refine candidates: 2 tracks x nccf_maxcands
 
@@ -305,26 +306,32 @@ __global__ void __launch_bounds__(PF_THREADS) yaapt_prefilter_kernel(const float
 }
 
 // ------------------------------------------------------------------------------------------------
-// 8192-point complex FFT in LDS, radix-2 decimation in time, 256 threads.  Input already stored in
-// bit-reversed order.  tw[k] = exp(-2*pi*i*k/8192), k < 4096 (host table, f64 -> f32).
+// 8192-point transform of a REAL frame in LDS.  The frame is packed two samples to a complex point,
+// z[m] = x[2m] + i x[2m+1], one 4096-point complex FFT (radix-2 decimation in time, input stored in bit-reversed
+// order) gives Z, and a wanted bin follows from Z[k] and Z[4096 - k] (fft_packed_mag below): half the points, half
+// the LDS (32 KB) and no imaginary half full of zeros carried through every pass.
+// tw = the staged table of yaapt_stage_twiddles_kernel over the host's tw[k] = exp(-2*pi*i*k/8192), k < 4096 (f64 -> f32).
 // ------------------------------------------------------------------------------------------------
-constexpr int FFT_THREADS = 1024;
-__device__ __forceinline__ int brev13(int j) { return (int)(__brev((unsigned)j) >> (32 - FFT_LOG)); }
+// 512 threads = 8 waves: a block's 32 KB let four of them share a CU, which is the CU's 32 waves (the waves are what hides
+// the LDS round trips of a pass); one radix-8 group per thread and pass.  What follows the FFT keeps its 256-thread shape.
+// (Measured: YAAPT on 32 x 5 s 2.08 ms; with 256 threads, two groups per thread, 83 VGPRs and 16 waves per CU, 2.12 ms.)
+constexpr int FFT_THREADS = 512;
+template <int LOG>
+__device__ __forceinline__ int brev(int j) { return (int)(__brev((unsigned)j) >> (32 - LOG)); }
 
-// One pass = NST consecutive radix-2 stages (s .. s+NST-1) done in registers on groups of 2^NST elements
-// spaced 2^(s-1) apart: the butterflies, their twiddles and their order of operations are exactly those of the
+// One pass = NST consecutive radix-2 stages (s .. s+NST-1) of the 2^LOG-point FFT done in registers on groups of 2^NST
+// elements spaced 2^(s-1) apart: the butterflies, their twiddles and their order of operations are exactly those of the
 // stage-by-stage loop, so the result is bit-identical to it — only the LDS round trips and barriers between
-// the stages of a pass are gone (13 -> 4-5 passes).
-template <int NST>
-__device__ __forceinline__ void fft8192_pass(float* re, float* im, const float2* __restrict__ tw, int s) {
+// the stages of a pass are gone (12 -> 3-4 passes).  T = threads of the block.
+template <int LOG, int T, int NST>
+__device__ __forceinline__ void fft_pass(float* re, float* im, const float2* __restrict__ tw, int s) {
+  constexpr int N = 1 << LOG;
   constexpr int R = 1 << NST;
   const int h = 1 << (s - 1);
-  // FFT_THREADS threads: the FFT kernels run 1024 (16 waves; LDS holds two such blocks per CU, so the waves of
-  // a block are what hides the LDS round trips of a pass); what follows the FFT keeps its 256-thread shape
 #pragma unroll 2
-  for (int k = 0; k < (FFT_N / R + FFT_THREADS - 1) / FFT_THREADS; ++k) {
-    const int i = threadIdx.x + FFT_THREADS * k;
-    if (FFT_N / R < FFT_THREADS && i >= FFT_N / R) break;
+  for (int k = 0; k < (N / R + T - 1) / T; ++k) {
+    const int i = threadIdx.x + T * k;
+    if (N / R < T && i >= N / R) break;
     const int pos = i & (h - 1);
     const int base = ((i >> (s - 1)) << (s - 1 + NST)) + pos;
     float xr[R], xi[R];
@@ -336,9 +343,9 @@ __device__ __forceinline__ void fft8192_pass(float* re, float* im, const float2*
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
       const int d = 1 << st;                              // partner distance in group slots at stage s + st
-      // staged table (yaapt_stage_twiddles_kernel): stage s + st's 2^(s + st - 1) twiddles tw[p * tstep] are contiguous from
-      // entry 2^(s + st - 1) - 1 on, so consecutive lanes (consecutive pos) read consecutive entries instead of a gather at
-      // stride tstep (64 cache lines per wave instruction at the middle stages)
+      // staged table (yaapt_stage_twiddles_kernel): stage s + st's 2^(s + st - 1) twiddles are contiguous from entry
+      // 2^(s + st - 1) - 1 on, whatever the size of the transform (entry (h - 1) + p = exp(-2 pi i p / 2h)), so consecutive
+      // lanes (consecutive pos) read consecutive entries instead of a gather at the stage's stride
       const float2* __restrict__ ts = tw + ((h << st) - 1);
 #pragma unroll
       for (int j = 0; j < R; ++j) {
@@ -363,40 +370,67 @@ __device__ __forceinline__ void fft8192_pass(float* re, float* im, const float2*
   __syncthreads();
 }
 
-// stages first .. 13 of the 8192-point radix-2 DIT FFT (input in bit-reversed order).
-// (Round 3, measured and not kept: the twiddles of a radix-8 pass in registers, requested one pass ahead — nlfer 268 -> 418 us;
-// the last pass computing only the wanted output bins, 7 of 24 butterfly results and 1 of 8 LDS writes — 229 -> 238 us at
-// the same occupancy.  What did pay: the per-stage contiguous twiddle table below, 268 -> 229 and 304 -> 222 us.)
-__device__ void fft8192_from(float* re, float* im, const float2* __restrict__ tw, int first) {
+// stages first .. LOG of the 2^LOG-point radix-2 DIT FFT (input in bit-reversed order).
+// (Round 3, on the 8192-point complex form, measured and not kept: the twiddles of a radix-8 pass in registers, requested one pass
+// ahead — nlfer 268 -> 418 us; the last pass computing only the wanted output bins, 7 of 24 butterfly results and 1 of 8 LDS writes —
+// 229 -> 238 us at the same occupancy.  What did pay: the per-stage contiguous twiddle table below, 268 -> 229 and 304 -> 222 us.)
+template <int LOG, int T>
+__device__ void fft_from(float* re, float* im, const float2* __restrict__ tw, int first) {
   int s = first;
-  const int lead = (FFT_LOG - first + 1) % 3;
-  if (lead == 1) { fft8192_pass<1>(re, im, tw, s); s += 1; }
-  if (lead == 2) { fft8192_pass<2>(re, im, tw, s); s += 2; }
-  for (; s <= FFT_LOG; s += 3) fft8192_pass<3>(re, im, tw, s);
+  const int lead = (LOG - first + 1) % 3;
+  if (lead == 1) { fft_pass<LOG, T, 1>(re, im, tw, s); s += 1; }
+  if (lead == 2) { fft_pass<LOG, T, 2>(re, im, tw, s); s += 2; }
+  for (; s <= LOG; s += 3) fft_pass<LOG, T, 3>(re, im, tw, s);
 }
 
-// Zero-padded real input of L <= 8192 >> z samples: in bit-reversed order the samples sit at multiples of 2^z
-// and the first z stages only copy each one over its block of 2^z (x + w*0 and x - w*0).  Fills re/im with that
-// state and returns the first stage left to do.  get(j) = sample j.
-template <typename Get>
-__device__ __forceinline__ int fft8192_load_padded(float* re, float* im, int L, Get get) {
-  const int z = L <= 1024 ? 3 : (L <= 2048 ? 2 : (L <= 4096 ? 1 : 0));
-  for (int i = threadIdx.x; i < FFT_N; i += FFT_THREADS) im[i] = 0.f;
-  // Element (j, r) = re[brev13(j) + r], j < 8192 >> z, r < 2^z.  The LDS bank of brev13(j) is set by the TOP 6 - z bits of j
-  // (bits 7 .. 12 - z reversed), so a wave that walks 64 consecutive j writes all its lanes to ONE bank (64-way conflict on
-  // every store; with 8000 blocks per launch this fill was a third of the FFT kernels' time).  Here a lane is (r, q):
-  // r = the low z bits, q = the top 6 - z bits of j; the 7 low bits of j come from (wave, round) — 64 distinct banks per store.
-  static_assert(FFT_THREADS == 1024, "16 waves x 8 rounds = the 128 low-bit values of j");
+// Packed, zero-padded real input of L samples, Lp = ceil(L / 2) <= 2^LOG >> z points (an odd L leaves the last imaginary part 0):
+// in bit-reversed order the points sit at multiples of 2^z and the first z stages only copy each one over its block of 2^z
+// (z + w*0 and z - w*0).  Fills re/im with that state, every element of both, and returns the first stage left to do.
+// get(j) = sample j.
+template <int LOG, int T, typename Get>
+__device__ __forceinline__ int fft_load_packed(float* re, float* im, int L, Get get) {
+  constexpr int N = 1 << LOG;
+  const int Lp = (L + 1) >> 1;
+  const int z = Lp <= N / 8 ? 3 : (Lp <= N / 4 ? 2 : (Lp <= N / 2 ? 1 : 0));
+  // Element (m, r) = re/im[brev(m) + r], m < N >> z, r < 2^z.  The low six address bits, the LDS bank, are r and, above it, the
+  // TOP 6 - z bits of m reversed (bits 6 .. 11 - z), so a wave that walks 64 consecutive m writes all its lanes to ONE bank
+  // (64-way conflict on every store; in the 8192-point form with 8000 blocks per launch such a fill was a third of the FFT kernels'
+  // time).  Here a lane is (r, q): r = its low z bits, q = the top 6 - z bits of m; the 6 low bits of m come from (wave, round).  A
+  // 4-byte store is banked modulo 32 within each half of the wave, which drops address bit 5 = bit 0 of q: that bit is the lane's
+  // half, the others come from the lane's bits z .. 4 — 32 distinct banks per half.
+  constexpr int WAVES = T / 64, ROUNDS = 64 / WAVES;
+  static_assert(LOG == 12 && T % 64 == 0 && WAVES * ROUNDS == 64, "waves x rounds = the 64 low-bit values of m");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & ((1 << z) - 1), q = lane >> z;
+  const int r = lane & ((1 << z) - 1), q = (((lane & 31) >> z) << 1) | (lane >> 5);
 #pragma unroll
-  for (int round = 0; round < 8; ++round) {
-    const int j = (q << 7) | (wave * 8 + round);
-    const float v = j < L ? get(j) : 0.f;
-    re[brev13(j) + r] = v;
+  for (int round = 0; round < ROUNDS; ++round) {
+    const int m = (q << 6) | (wave * ROUNDS + round);
+    const int j = 2 * m;
+    const float a = j < L ? get(j) : 0.f;
+    const float b = j + 1 < L ? get(j + 1) : 0.f;
+    const int at = brev<LOG>(m) + r;
+    re[at] = a;
+    im[at] = b;
   }
   __syncthreads();
   return z + 1;
+}
+
+// |X[k]|, k < 4096, of the 8192-point transform X of the real frame whose packed transform Z lies in re/im ("untangle"):
+//   E[k] = (Z[k] + conj Z[4096 - k]) / 2    the transform of the even samples
+//   O[k] = (Z[k] - conj Z[4096 - k]) / 2i   the transform of the odd ones
+//   X[k] = E[k] + w^k O[k], w = exp(-2 pi i / 8192): the last stage's butterfly of the 8192-point form with its twiddle, entry
+//   (4096 - 1) + k of the staged table;  X[0] = Re Z[0] + Im Z[0].
+// The halving is an exact multiply; one rounding each in E and O, then the four-multiply product and the two additions of a butterfly.
+__device__ __forceinline__ float fft_packed_mag(const float* re, const float* im, const float2* __restrict__ tw, int k) {
+  if (k == 0) return hypotf(re[0] + im[0], 0.f);
+  const float ar = re[k], ai = im[k], br = re[FFT_NP - k], bi = im[FFT_NP - k];
+  const float er = (ar + br) * 0.5f, ei = (ai - bi) * 0.5f;
+  const float pr = (ai + bi) * 0.5f, pi = (br - ar) * 0.5f;
+  const float2 w = tw[(FFT_NP - 1) + k];
+  const float tr = pr * w.x - pi * w.y;
+  const float ti = pr * w.y + pi * w.x;
+  return hypotf(er + tr, ei + ti);
 }
 
 // staged twiddles: out[(h - 1) + p] = tw[p * (4096 / h)] for every stage half-size h = 1, 2, ... 4096 and p < h (8191 entries):
@@ -415,16 +449,16 @@ __global__ void __launch_bounds__(FFT_THREADS) yaapt_nlfer_kernel(const float* _
                                                          const int* __restrict__ U, const Plan P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* re = lds;
-  float* im = lds + FFT_N;
+  float* im = lds + FFT_NP;
   __shared__ float red[8];
   const int f = blockIdx.x, b = blockIdx.y;
   if (f >= ulen(U, b, 2, P.nframes)) return;
   const float* x = filt + ((size_t)b * 2 + 0) * P.Lz + (size_t)f * P.frame_jump;
-  const int first = fft8192_load_padded(re, im, P.frame_size, [&](int j) { return x[j] * hann[j]; });
-  fft8192_from(re, im, tw, first);
+  const int first = fft_load_packed<FFT_LOG, FFT_THREADS>(re, im, P.frame_size, [&](int j) { return x[j] * hann[j]; });
+  fft_from<FFT_LOG, FFT_THREADS>(re, im, tw, first);
   if (threadIdx.x >= 256) return;          // whole waves: the reduction keeps its 256-thread order
   float part = 0.f;
-  for (int k = P.nl_lo + threadIdx.x; k < P.nl_hi; k += 256) part += hypotf(re[k], im[k]);
+  for (int k = P.nl_lo + threadIdx.x; k < P.nl_hi; k += 256) part += fft_packed_mag(re, im, tw, k);
   const float tot = block_sum256(part, red);
   if (threadIdx.x == 0) e_raw[(size_t)b * P.nframes + f] = tot;
 }
@@ -448,18 +482,18 @@ __global__ void __launch_bounds__(256) yaapt_energy_norm_kernel(const float* __r
 
 // spectral track, per voiced frame: 1120 samples x kaiser, minus mean -> FFT -> |X| -> SHC -> peaks
 // cand layout: [b][8][nframes] = pitch[0..3], merit[0..3]
-// Two kernels (round 3): the FFT block holds 64 KB of LDS and 16 waves, the SHC / peak search after it is a 256-thread,
-// then one-thread, latency-bound tail of about the same duration — kept in one kernel it pinned those 64 KB for twice as
-// long, and two such blocks leave no room on a CU for the generator's conv blocks of the other job streams.  The FFT kernel
-// now ends at the magnitude window (n_mag <= 1280 floats per frame, through the workspace); the tail runs with 6 KB of LDS.
-// Same arithmetic in the same order: the F0 track is unchanged bit for bit.
+// Two kernels (round 3): the FFT block held 64 KB of LDS and 16 waves (32 KB and 8 since the packed form), the SHC / peak search
+// after it is a 256-thread, then one-thread, latency-bound tail of about the same duration — kept in one kernel it pinned that LDS
+// for twice as long, and the FFT blocks leave little room on a CU for the generator's conv blocks of the other job streams.  The FFT
+// kernel ends at the magnitude window (n_mag <= 1280 floats per frame, through the workspace); the tail runs with 6 KB of LDS.
+// Same arithmetic in the same order: the F0 track was unchanged bit for bit by the split.
 constexpr int SPEC_MAGP = 5 * 256;      // floats per frame of the magnitude hand-over (the kernels' 5 x 256 window)
 __global__ void __launch_bounds__(FFT_THREADS) yaapt_spec_kernel(const float* __restrict__ filt, const float* __restrict__ kaiser,
                                                         const float2* __restrict__ tw, const int* __restrict__ vuv,
                                                         float* __restrict__ magbuf, const int* __restrict__ U, const Plan P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* re = lds;
-  float* im = lds + FFT_N;
+  float* im = lds + FFT_NP;
   __shared__ float red[8];
   const int tid = threadIdx.x;
   const int f = blockIdx.x, b = blockIdx.y;
@@ -475,19 +509,12 @@ __global__ void __launch_bounds__(FFT_THREADS) yaapt_spec_kernel(const float* __
     if (tid < 256 && j < P.nframe_size) part += x[j] * kaiser[j];
   }
   const float mean = block_sum256(part, red) / (float)P.nframe_size;
-  const int first = fft8192_load_padded(re, im, P.nframe_size, [&](int j) { return x[j] * kaiser[j] - mean; });
+  const int first = fft_load_packed<FFT_LOG, FFT_THREADS>(re, im, P.nframe_size, [&](int j) { return x[j] * kaiser[j] - mean; });
   const int n_mag = P.min_shc * (P.nharm + 1) + (P.max_shc - P.min_shc) * (P.nharm + 1) + P.wl;  // exclusive bound
-  fft8192_from(re, im, tw, first);
-  if (tid >= 256) return;
+  fft_from<FFT_LOG, FFT_THREADS>(re, im, tw, first);
   // magnitude[i] = i < half_wl ? 0 : |X[i - half_wl]|
   float* mo = magbuf + ((size_t)b * nf + f) * SPEC_MAGP;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const int i = tid + 256 * k;
-    float v = 0.f;
-    if (i < n_mag && i >= P.half_wl) v = hypotf(re[i - P.half_wl], im[i - P.half_wl]);
-    if (i < n_mag) mo[i] = v;
-  }
+  for (int i = tid; i < n_mag; i += FFT_THREADS) mo[i] = i >= P.half_wl ? fft_packed_mag(re, im, tw, i - P.half_wl) : 0.f;
 }
 
 __global__ void __launch_bounds__(256) yaapt_spec_peaks_kernel(const float* __restrict__ magbuf, const int* __restrict__ vuv,
@@ -1119,6 +1146,8 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   SAT_REQUIRE(P.frame_size > 15, "Frame length value %d is too short.", P.frame_size);
   SAT_REQUIRE(P.frame_size < 2048, "Frame length value %d exceeds the limit.", P.frame_size);
   SAT_REQUIRE(P.nframe_size <= 5 * 256 && P.frame_size <= FFT_N, "yaapt: frame_length too long for the spectral kernel");
+  // the bins read off the packed transform: Z[k] and Z[4096 - k], 0 <= k < 4096 (the SHC's are below 5 * 256, next requirement but one)
+  SAT_REQUIRE(P.nl_lo >= 0 && P.nl_hi <= FFT_NP, "yaapt: NLFER bins %d..%d outside the half spectrum", P.nl_lo, P.nl_hi);
   SAT_REQUIRE(P.max_shc <= 256 && P.pk_max_lag + 1 < 256 && P.pk_min_lag + P.pk_center + 1 >= 1 &&
                   P.pk_min_lag - 0 >= 0, "yaapt: SHC range out of the 256-bin kernel window");
   SAT_REQUIRE(P.min_shc * (P.nharm + 1) + (P.max_shc - P.min_shc) * (P.nharm + 1) + P.wl <= 5 * 256,
@@ -1160,7 +1189,7 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   if (pf_vec) hipLaunchKernelGGL(yaapt_prefilter_kernel<true>, dim3((B + 31) / 32), dim3(PF_THREADS), 0, s, wav, filt, U, P, B);
   else hipLaunchKernelGGL(yaapt_prefilter_kernel<false>, dim3((B + 31) / 32), dim3(PF_THREADS), 0, s, wav, filt, U, P, B);
   SAT_LAUNCH_CHECK("yaapt_prefilter_kernel");
-  const size_t fft_lds = 2 * FFT_N * sizeof(float);
+  const size_t fft_lds = 2 * FFT_NP * sizeof(float);
   static std::atomic<uint64_t> attr_done{0};      // per device
   int dev;
   if (attr_needed_on_current_device(attr_done, &dev)) {
