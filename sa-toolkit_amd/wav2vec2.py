@@ -242,7 +242,11 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         return W
 
     # ---- wav2vec2 forward: [B, n] -> last layer output [B, 1024, frames] ------------------------
-    def w2v2_features(self, wav):
+    def w2v2_features(self, wav, hook=None):
+        """`hook(name, f32 tensor or None, planes or None)`, if given, sees the intermediates (the mirror of oracle.convert.forward's
+        `hook`): "ln0" (conv 0 + its LayerNorm), "conv1" / "ln1" .. "conv6" / "ln6", "proj", "pos" (the input of layer 0), "last".  A
+        stage that hands on split planes only passes None for the f32 tensor; the LayerNorms before a stride-2 conv pass their
+        phase-split form.  No launch depends on it."""
         W = self._prepare_w2v2(wav.device)
         mm = self._mm_mode
         B, n = wav.shape
@@ -263,6 +267,8 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
                 x, xs = ops.layernorm_ch(x, e["g"], e["beta"], gelu=True, split_phases=True, planes=True, want_f32=False)
             else:
                 x, xs = ops.layernorm_ch(x, e["g"], e["beta"], gelu=True, split_phases=not last), None
+            if hook:
+                hook(f"ln{i}", None if xs is not None else x, xs)
             if not last:
                 nxt = W["fe"][i + 1]
                 if xs is not None and "w_wrap" in nxt:
@@ -271,6 +277,8 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
                 else:
                     x = ops.conv1d(x, nxt["w"], 512, nxt["k"], bias=nxt["b"], pad_left=0, pad_right=0, t_out=fe_len[i + 1], mode=mm,
                                    x_split=xs)
+                if hook:
+                    hook(f"conv{i + 1}", x, None)
         T = x.shape[2]
         # feature projection
         if planes:
@@ -278,6 +286,8 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         else:
             x, xs = ops.layernorm_ch(x, W["fp"]["g"], W["fp"]["beta"]), None
         x = ops.conv1d(x, W["fp"]["w"], 1024, 1, bias=W["fp"]["b"], mode=mm, x_split=xs)
+        if hook:
+            hook("proj", x, None)
         # positional conv (grouped, k = 128, pad 64, last sample dropped) + GELU, added to x
         if "pieces" in W["pos"]:
             y = None
@@ -289,6 +299,8 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         else:
             x = ops.conv1d(x, W["pos"]["w"], 1024, 128, bias=W["pos"]["b"], pad_left=64, pad_right=63, groups=16,
                            gelu=True, post_res=x)
+        if hook:
+            hook("pos", x, None)
         # NO encoder-level LayerNorm here: torchaudio builds Transformer(layer_norm_first=not encoder_layer_norm_first),
         # so `encoder.transformer.layer_norm` runs after the stack in forward() and not at all in
         # get_intermediate_outputs / extract_features, whose [-1] the reference takes (tdnnf_wav2vec2_vq.py:295-297);
@@ -347,6 +359,8 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
             else:
                 h = ops.conv1d(h, L["f1_w"], 4096, 1, bias=L["f1_b"], gelu=True, mode=mm)
                 x = ops.conv1d(h, L["f2_w"], 1024, 1, bias=L["f2_b"], res=x, mode=mm)
+        if hook:
+            hook("last", x, None)
         return x
 
     @staticmethod

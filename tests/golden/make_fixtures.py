@@ -426,6 +426,67 @@ def main():
         h.remove()
         np.savez_compressed(os.path.join(GOLD, "fx_w2v2_long.npz"), **out)
         print("w2v2_long:", {k: v.shape for k, v in out.items()})
+    if want("w2v2_lengths"):
+        # the wav2vec2 tag on the length catalogue of tests/w2v2_lengths.py (the recipe of the "w2v2" section: the reference's own Net, the
+        # stand-in factory, the conditioned synthetic checkpoint): per entry the get_bn shape (its values up to 65 frames), the VQ indices, the two best distances'
+        # gap (and the best distance and the norm of the VQ's input: the flip rule of the tests needs them), every 16th channel of the last layer; for the parity
+        # set also every 4th channel of the feature extractor's output; the exception type where the reference raises; convert() at
+        # three lengths with the reference's own get_f0
+        import torchaudio
+        from oracle import wav2vec2 as ow
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import w2v2_lengths as WL
+        torchaudio.models.wav2vec2.model._factory = ow.build_wav2vec2
+        name2 = "bn_tdnnf_wav2vec2_vq_48"
+        net2 = build_reference_model(ref, name2)
+        st2, _ = synthetic.checkpoint(WL.TAG)
+        net2.load_state_dict(st2["base_model_state_dict"], strict=True)
+        net2.eval()
+        pre = net2.bn_extractor.preprocessor
+        acts = {}
+        h = net2.bn_extractor.tdnnfs[2].bottleneck_func.quant.register_forward_hook(
+            lambda m, i, o: acts.update(idx=o[5].detach(), dist=o[4].detach(), znorm=i[0].detach().norm(dim=-1)))
+        out = {}
+        with torch.no_grad():
+            for e in WL.ENTRIES:
+                w = e.wav()
+                try:
+                    bn = net2.get_bn(w.clone())
+                except Exception as ex:
+                    out[f"{e.name}/raises"] = np.array(type(ex).__name__)
+                    print(f"w2v2_lengths: {e.name} (n = {e.n}) raises {type(ex).__name__}: {ex}")
+                    continue
+                out[f"{e.name}/bn_shape"] = np.array(bn.shape, dtype=np.int32)
+                if e.T <= 65:
+                    out[f"{e.name}/bn_sub"] = bn[:, ::16, :].numpy()        # [B, 16, T + 1]: every 16th of the 256 dimensions
+                out[f"{e.name}/idx"] = acts["idx"].reshape(e.B, -1).numpy().astype(np.int16)
+                srt = acts["dist"].sort(1)[0]
+                out[f"{e.name}/margin"] = (srt[:, 1] - srt[:, 0]).reshape(e.B, -1).numpy()
+                out[f"{e.name}/d1"] = srt[:, 0].reshape(e.B, -1).numpy()
+                out[f"{e.name}/znorm"] = acts["znorm"].reshape(e.B, -1).numpy()          # |z| of the VQ's input [N, T, C], per frame
+                out[f"{e.name}/w2v2_last_sub"] = pre.extract_features(w)[0][-1][:, :, ::16].numpy()
+                if e.edge == "parity":
+                    fe = pre.feature_extractor(w)
+                    fe = fe[0] if isinstance(fe, tuple) else fe
+                    assert fe.shape == (1, 3, 512)
+                    out[f"{e.name}/fe_sub"] = fe[:, :, ::4].numpy()
+            for name, step in WL.CONVERT:
+                e = WL.BY_NAME[name]
+                try:
+                    out[f"{name}/convert"] = net2.convert(e.wav(), target=WL.convert_targets(net2.spk, e.B)).numpy()[..., ::step]
+                except Exception as ex:
+                    out[f"{name}/convert_raises"] = np.array(type(ex).__name__)
+                    print(f"w2v2_lengths: convert() of {name} raises {type(ex).__name__}: {ex}")
+        h.remove()
+        # float32 noise does not compress: what is recorded adds up to 0.8 MB, so it goes into three files of under 500 KB each
+        # (WL.fixture() reads them as one): the parity set, the batches with the convert() waveforms, everything else
+        parity, batches = {e.name for e in WL.PARITY}, {e.name for e in WL.BATCHES}
+        part = lambda k: "_parity" if k.split("/")[0] in parity else "_batches" if k.split("/")[0] in batches or k.split("/")[1].startswith("convert") else ""
+        for sfx in ("", "_parity", "_batches"):
+            path = os.path.join(GOLD, f"fx_w2v2_lengths{sfx}.npz")
+            np.savez_compressed(path, **{k: v for k, v in out.items() if part(k) == sfx})
+            print("w2v2_lengths:", path, os.path.getsize(path), "bytes")
+            assert os.path.getsize(path) < 500_000
     print("fixtures written to", GOLD)
 
 

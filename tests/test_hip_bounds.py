@@ -1292,6 +1292,50 @@ conv_rows("k1 stride 2 wrapped", 256, "gemm_f16x3_ring16_kernel", cin=192, cout=
           shapes=[(1, 1), (3, 255), (1, 256), (3, 257), (3, 677)])
 
 
+def pos_piece_case(B, T, pad_left, Cc=1024, groups=16, k=11, bound=3e-5):
+    """one of the twelve shifted 11-tap pieces the split-f16 path makes of the wav2vec2 positional conv (wav2vec2.py: grouped, 16 groups, f32 input,
+    pad_left = 64 - 11 s, pad_right = 10 - pad_left, `res` and `out` the SAME tensor from the second piece on): piece 0 (pad_left 64) has the bias and
+    writes a fresh tensor, the last (pad_left -57) the GELU.  A negative pad_left starts the window right of the output frame; at these T the window
+    lies wholly left of the sequence (64 at T <= 54), wholly right of it (-57 at T <= 57) or straddles an end (9, -2).  `bound`: conv_case's"""
+    _, ops, _ = _sat()
+    c = Case()
+    first, last = pad_left == 64, pad_left == -57
+    x = rand(B, Cc, T, seed=T + Cc)
+    w = rand(Cc, Cc // groups, k, seed=2, scale=(Cc // groups * k) ** -0.5)
+    b = rand(Cc, seed=3)
+    y0 = rand(B, Cc, T, seed=5)
+    wp, attrs = _pack(w, 1, groups=groups)
+    c.inp("x", x)
+    c.inp("w", wp)
+    c.inp("bias", b)
+    if first:
+        c.out("y", (B, Cc, T))
+    else:
+        c.inout("y", y0)
+
+    def call(t):
+        ops.conv1d(t["x"], _attrs(t["w"], attrs), Cc, k, bias=t["bias"] if first else None, pad_left=pad_left, pad_right=k - 1 - pad_left, groups=groups, mode=1,
+                   res=None if first else t["y"], gelu=last, out=t["y"])
+    c.call = call
+
+    def ref(t):
+        xp = torch.zeros(B, Cc, T + k - 1, dtype=torch.float64)          # xp[i] = x[i - pad_left] where that is a frame: F.pad cannot crop more than there is
+        for i in range(T + k - 1):
+            if 0 <= i - pad_left < T:
+                xp[:, :, i] = x[:, :, i - pad_left].double()
+        v = F.conv1d(xp, w.double(), b.double() if first else None, groups=groups)
+        if not first:
+            v = v + y0.double()
+        bounded(f"conv1d positional piece pad_left {pad_left}", t["y"], F.gelu(v) if last else v, bound)
+    c.ref = ref
+    return c
+
+
+@row("sat_conv1d_f32", "f16x3 positional-conv piece groups 16 k11 res=out", [(2, T, pl) for T in (1, 10, 53, 64) for pl in (64, 9, -2, -57)])
+def _(B, T, pad_left):
+    return pos_piece_case(B, T, pad_left)
+
+
 def ups_case(B, T, cin, cout, k, u, *, mode=0, planes=False, grouped=False, mask=0, sidecar=False, family=None, options=(), bound=3e-5):
     """ConvTranspose1d(k, stride u, padding (k - u) / 2) as the polyphase conv of sat_conv1d_f32 (up = u): f32 in and out, planes to planes through the
     LDS-transposed epilogue, or the phase-grouped rows of the ring (up_grouped, with and without the zero-tap mask)"""

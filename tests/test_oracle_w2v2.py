@@ -38,6 +38,56 @@ def test_extract_bn_matches_reference(gold, w2v2_state):
     assert np.abs(bn.permute(0, 2, 1).numpy() - fx["harm01_16000/bn"])[:, :, agree[0] & agree[1]].max() < 2e-4
 
 
+@pytest.fixture(scope="module")
+def w2v2_oracle(w2v2_state):
+    """(ASR-BN state dict, the restated wav2vec2 model loaded once) for the length sweep"""
+    state, _ = w2v2_state
+    asr, _ = oconv.split_state_dict(state["base_model_state_dict"])
+    om = ow.Wav2Vec2Restated(24)
+    om.load_state_dict({k[len("preprocessor."):]: v for k, v in asr.items() if k.startswith("preprocessor.")})
+    om.eval()
+    return asr, om
+
+
+@pytest.fixture(scope="module")
+def lengths_fx(gold):
+    import w2v2_lengths as WL
+    return WL.fixture(gold)
+
+
+def _length_subset():
+    import w2v2_lengths as WL
+    return WL.ORACLE_SUBSET
+
+
+@pytest.mark.parametrize("entry", _length_subset(), ids=lambda e: e.name)
+def test_extract_bn_matches_reference_on_the_length_catalogue(entry, w2v2_oracle, lengths_fx):
+    """the oracle's plumbing at the lengths of tests/w2v2_lengths.py (even frame counts into the stride-2 convs, 1 .. 65 frames, the
+    tiled right pad of pad_input at B = 3 where it is longer than the utterance) against the reference's own Net, at the bars of
+    test_extract_bn_matches_reference"""
+    asr, om = w2v2_oracle
+    fx = lengths_fx
+    aux, acts = {}, {}
+    bn = otd.extract_bn_w2v2(asr, entry.wav(), aux=aux, hook=lambda n, t: acts.__setitem__(n, t), model=om)
+    assert list(bn.permute(0, 2, 1).shape) == fx[f"{entry.name}/bn_shape"].tolist()
+    assert np.abs(acts["w2v2"][:, :, ::16].numpy() - fx[f"{entry.name}/w2v2_last_sub"]).max() < 1e-4
+    assert (aux["idx"].reshape(entry.B, -1).numpy() == fx[f"{entry.name}/idx"]).all()
+    assert np.abs(bn.permute(0, 2, 1)[:, ::16].numpy() - fx[f"{entry.name}/bn_sub"]).max() < 2e-4
+    if entry.edge == "parity":
+        with torch.no_grad():
+            fe = om.feature_extractor(entry.wav())
+        assert np.abs(fe[:, :, ::4].numpy() - fx[f"{entry.name}/fe_sub"]).max() < 1e-5
+
+
+def test_too_short_raises_like_the_reference(w2v2_oracle, lengths_fx):
+    import w2v2_lengths as WL
+    asr, om = w2v2_oracle
+    for e in WL.TOO_SHORT:
+        with pytest.raises(Exception) as ei:
+            otd.extract_bn_w2v2(asr, e.wav(), model=om)
+        assert type(ei.value).__name__ == str(lengths_fx[f"{e.name}/raises"])
+
+
 def test_frame_counts(gold):
     shapes = gold.json("fx_shapes_w2v2.json")
     assert shapes.pop("forward_2x32000") == [2, 66, 3280]      # the reference's own validate_model assertion (66 frames)
