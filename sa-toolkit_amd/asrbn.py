@@ -10,6 +10,7 @@ conv over frames (kernel = context_len, stride = subsampling_factor) into the bo
 BatchNorm1d(affine=False) and the ReLU (chain/nn.py:338-347).  Both run on the fused MFMA conv
 kernel; the VQ bottleneck (chain/nn.py:402-476) has its own kernel.
 """
+import collections
 import math
 import os
 
@@ -242,6 +243,71 @@ class _LayerCache:
     __slots__ = ("wB", "bB", "wA", "bA", "scale", "shift", "codebook", "modeA", "modeB")
 
 
+#: the forms a TDNNF layer is launched in ("TDNNF layer forms"): the 1.5x unfold layer | ONE call (sat_tdnnf_layer_f32) | context-
+#: free subsampling on planes, the 1x1 product on EVERY frame | the same on a gathered f32 copy | two sat_conv1d_f32 calls (the rest)
+UNFOLD15, ONE_CALL, SUB_PLANES, SUB_GATHER, TWO_CALL = "unfold15", "one_call", "sub_planes", "sub_gather", "two_call"
+
+#: how one layer of a planned run is launched.  planes_in: linearB reads the predecessor's split planes; planes_out: the layer writes
+#: planes of its output; z_planes: linearA reads the bottleneck from planes; reads_f32: the layer NEEDS its f32 input written
+#: (False: it can run from the planes alone; handed a written input, the one-call layer still takes its bypass from that);
+#: skip_f32: its f32 output is not stored (an unwritten shape carrier is handed on); x_unwritten: its f32 input is such a carrier (the
+#: one-call layer is given x = NULL and rebuilds its bypass from the planes); bottleneck_only: the run ends at its bottleneck
+_LayerPlan = collections.namedtuple("_LayerPlan", "form planes_in planes_out z_planes reads_f32 skip_f32 x_unwritten bottleneck_only")
+
+
+def plan_layers(layers, caches, planes_only, to_bottleneck, planes=False):
+    """One `_LayerPlan` per layer of a run of TDNNF layers, from what is fixed once the weights are packed (context, subsampling,
+    widths, bypass, codebook, modeA / modeB) and from whether the predecessor hands on planes (`planes`: the run's input does).
+    to_bottleneck: the run ends at the LAST layer's bottleneck (`_run_stack`) and, with `planes_only`, a layer whose successor never
+    reads f32 skips its f32 store; otherwise every layer runs through and every f32 output is stored (skipping changes bits)."""
+    plan, n = [], len(layers)
+    for i, (lay, c) in enumerate(zip(layers, caches)):
+        last = to_bottleneck and i + 1 == n
+        need_z = last or c.codebook is not None              # the bottleneck itself is wanted in f32: read out, or quantised
+        feat, bott, sub = lay.feat_dim, lay.bottleneck_dim, lay.subsampling_factor
+        split_in = planes and c.modeB == 1 and feat % 16 == 0
+        planes_out, z_planes = not last and c.modeA == 1 and lay.out_dim % 16 == 0, False
+        if sub == 1.5:                                       # chain/nn.py:267-304: windows of the flattened input every 1.5 frames
+            if lay.context_len != 1 or need_z:
+                raise _lib.SatError("TDNNF plan: a layer with subsampling_factor 1.5 has context 1, no quantiser, and is not the bottleneck layer")
+            form, planes_in, reads = UNFOLD15, False, True
+        elif int(sub) == 1 and not need_z and c.modeA == c.modeB:
+            form, planes_in, z_planes = ONE_CALL, split_in, c.modeB == 1 and bott % 16 == 0
+            reads = not (planes_in and z_planes and planes_out)       # (else x also carries the bypass)
+        elif c.modeB == 1 and int(sub) > 1:
+            # split-f16 kernels are stride 1 (`_layer_cache`: context 1 here); the strided bypass reads the f32 input
+            if planes and feat % 64 == 0 and bott % 16 == 0 and not need_z:
+                form, planes_in, z_planes, reads = SUB_PLANES, True, True, lay.use_bypass
+            else:
+                form, planes_in, reads = SUB_GATHER, False, True
+        else:
+            form, planes_in = TWO_CALL, split_in and int(sub) == 1      # read-out / VQ layer, linearB in exact f32, strided f32
+            reads = not (planes_in and last)
+        plan.append(_LayerPlan(form, planes_in, planes_out, z_planes, reads, False, False, last))
+        planes = planes_out
+    if planes_only and to_bottleneck:
+        for i in range(n - 1):
+            p, lay = plan[i], layers[i]
+            # (a one-call layer on planes throughout; its own bypass comes from planes or does not exist)
+            if (p.form == ONE_CALL and lay.feat_dim % 16 == 0 and p.z_planes and p.planes_out and (p.planes_in or not lay.use_bypass)
+                    and not plan[i + 1].reads_f32):
+                plan[i], plan[i + 1] = p._replace(skip_f32=True), plan[i + 1]._replace(x_unwritten=True)
+    check_plan(plan)
+    return plan
+
+
+def check_plan(plan):
+    """an f32 tensor that is not written must not be read: refused here, before anything is launched"""
+    for i, p in enumerate(plan):
+        nxt = plan[i + 1] if i + 1 < len(plan) else None
+        if p.skip_f32 and (nxt is None or nxt.reads_f32 or not nxt.planes_in):
+            raise _lib.SatError(f"TDNNF plan: layer {i} skips its f32 store, but " +
+                                ("no layer takes its planes" if nxt is None else f"layer {i + 1} reads its f32 input"))
+        if p.x_unwritten != (i > 0 and plan[i - 1].skip_f32):
+            raise _lib.SatError(f"TDNNF plan: layer {i} is told its f32 input is " + ("unwritten, but its predecessor stores it (or it has none)"
+                                                                                     if p.x_unwritten else "written, but its predecessor skips that store"))
+
+
 class _TdnnfBase(nn.Module):
     """shared machinery of the two ASR-BN nets: TDNNF stack forward on the HIP kernels"""
 
@@ -339,109 +405,86 @@ class _TdnnfBase(nn.Module):
     #: planes; sat_tdnnf_layer_f32 with x = y = NULL): SATOOLS_AMD_TDNNF_PLANES_ONLY=0 keeps the f32 tensors
     tdnnf_planes_only = os.environ.get("SATOOLS_AMD_TDNNF_PLANES_ONLY", "1") != "0"
 
-    @staticmethod
-    def _takes_planes(lay, c, channels, need_z=False):
-        """does `_tdnnf_layer` read this layer's input from split planes alone (never the f32 tensor)?  A plain layer does (linearB and,
-        inside sat_tdnnf_layer_f32, the bypass); a subsampling layer only when it has no bypass (its strided bypass reads the f32 input)"""
-        sub = lay.subsampling_factor
-        if c.modeB != 1 or c.modeA != 1 or channels % 16 or sub == 1.5:
-            return False
-        if int(sub) == 1:
-            # (the layer with the quantiser inside / the bottleneck read-out multiplies the planes and has no bypass to take from f32)
-            return need_z or (c.codebook is None and lay.bottleneck_dim % 16 == 0 and lay.out_dim % 16 == 0)
-        return (not need_z and not lay.use_bypass and channels % 64 == 0 and lay.bottleneck_dim % 16 == 0 and c.codebook is None)
+    def _planned(self, through):
+        """The planned run of the packed weights as they are now (after `_prepare`; through: after `_prepare_full`), memoised per cache
+        list and `tdnnf_planes_only` — a precision flip or frozen.load_frozen installs another list.  through = False: [(layer, cache,
+        plan)] up to the last stack layer's bottleneck; True: {"stack", "after": such lists run through, "prefinal": one per head}."""
+        memo, key = self.__dict__.setdefault("_plans", {}), (id(self._cache), self.tdnnf_planes_only, through)
+        if key in memo:                 # (an entry holds its cache list, so the id stays that list's)
+            return memo[key][1]
 
-    def _plain_on_planes(self, lay, c, channels):
-        """a layer `_tdnnf_layer` serves by sat_tdnnf_layer_f32 with planes in, planes out and the bottleneck as planes"""
-        return (int(lay.subsampling_factor) == 1 and lay.subsampling_factor != 1.5 and c.codebook is None and c.modeA == 1 and c.modeB == 1 and
-                channels % 16 == 0 and lay.bottleneck_dim % 16 == 0 and lay.out_dim % 16 == 0)
-
-    def _tdnnf_layer(self, lay, c, x, xs=None, return_bottleneck=False, want_aux=False, row_frames=None, tie=None, skip_f32=False, x_valid=True):
-        """x [B, feat, T] -> [B, out, T'] (or the bottleneck [B, bott, T']).  In split-f16 mode the layers
-        hand their activations on as split planes as well (`xs`, csrc/conv_f16x3.hip): linearB then
-        stages its 1024 x 3 input with 16-byte copies and linearA reads the bottleneck from planes; the
-        f32 tensor stays for the bypass connection.  Returns (y, planes of y or None).
-        skip_f32: the f32 output is not stored (y is then an unwritten shape carrier: the successor takes the planes); x_valid = False:
-        `x` is such a carrier and the bypass is rebuilt from `xs` — both only where _plain_on_planes holds (_run_stack decides)."""
-        ctx, sub = lay.context_len, int(lay.subsampling_factor)
-        B = x.shape[0]
-        if lay.subsampling_factor == 1.5:
-            # chain/nn.py:267-304: windows of the flattened input every 1.5 frames + the add_padd bypass
-            assert ctx == 1 and not return_bottleneck and c.codebook is None
-            win, byp = ops.tdnnf_unfold15(x)
-            if row_frames is not None:
-                # ragged rows: the reference's bypass of this layer takes int(T / 1.5) frames and zero-fills the rest of
-                # the windows (chain/nn.py:294-304) — T being the row's OWN frame count, not the padded batch's
-                for i, n in enumerate(row_frames):
-                    byp[i, :, int(n / 1.5):] = 0
-            z = ops.conv1d(win, c.wB, lay.bottleneck_dim, 1, bias=c.bB, pad_left=0, pad_right=0, mode=c.modeB)
-            kw = dict(res=byp, res_scale=lay.bypass_scale) if lay.use_bypass else {}
-            ys = ops.split_like(B, lay.out_dim, z.shape[2], x.device) if (c.modeA == 1 and lay.out_dim % 16 == 0) else None
-            y = ops.conv1d(z, c.wA, lay.out_dim, 1, bias=c.bA, ch_scale=c.scale, ch_shift=c.shift, relu=True, mode=c.modeA,
-                           y_split=ys, y_split_slope=1.0, **kw)
-            return y, ys
-        planes_in = c.modeB == 1 and sub == 1 and xs is not None and x.shape[1] % 16 == 0
-        need_z = c.codebook is not None or return_bottleneck
-        if sub == 1 and not need_z and c.modeA == c.modeB and c.modeB in (0, 1):
-            # the plain layer (no subsampling, no quantiser inside): ONE call across the C-ABI (sat_tdnnf_layer_f32) — linearB, linearA with
-            # bypass + BatchNorm + ReLU; on split planes the bottleneck exists only as planes
-            t_q = x.shape[2] - (ctx - 1)
-            planes = c.modeB == 1 and lay.bottleneck_dim % 16 == 0
-            zs = ops.split_like(B, lay.bottleneck_dim, t_q, x.device) if planes else None
-            ys = ops.split_like(B, lay.out_dim, t_q, x.device) if (c.modeA == 1 and lay.out_dim % 16 == 0) else None
-            y = ops.tdnnf_layer(x, c.wB, c.bB, c.wA, c.bA, lay.bottleneck_dim, lay.out_dim, ctx, bn_scale=c.scale, bn_shift=c.shift,
-                                bypass_scale=float(lay.bypass_scale) if lay.use_bypass else 0.0, mode=c.modeB,
-                                x_split=xs if planes_in else None, y_split=ys, z_split=zs, no_y=skip_f32, bypass_from_planes=not x_valid)
-            return y, ys
-        assert x_valid or (c.modeB == 1 and xs is not None), "an unwritten f32 input reached a layer that reads it"
-
-        zs = None
-        if planes_in and not need_z and lay.bottleneck_dim % 16 == 0:
-            t_q = x.shape[2] - (ctx - 1)
-            zs = ops.split_like(B, lay.bottleneck_dim, t_q, x.device)
-            z = ops.conv1d(x, c.wB, lay.bottleneck_dim, ctx, bias=c.bB, pad_left=0, pad_right=0, mode=1,
-                           x_split=xs, y_split=zs, y_split_slope=1.0, no_y=True)     # z: shape carrier only
-        elif c.modeB == 1 and sub > 1 and xs is not None and x.shape[1] % 64 == 0 and lay.bottleneck_dim % 16 == 0 and not need_z:
-            # context-free subsampling layer on split planes: the 1x1 product on EVERY frame (the GEMM kernels read the planes the
-            # previous layer wrote: 8 x fewer bytes than the strided f32 copy of x the stride-1 kernels needed, round 6), every
-            # sub-th frame of the 128-row result kept and handed on as planes
-            z_all = ops.conv1d(x, c.wB, lay.bottleneck_dim, 1, bias=c.bB, pad_left=0, pad_right=0, mode=1, x_split=xs)
-            z = z_all[:, :, ::sub].contiguous()
-            zs = ops.act_split(z, 1.0)
-        elif c.modeB == 1 and sub > 1:
-            z = ops.conv1d(x[:, :, ::sub].contiguous(), c.wB, lay.bottleneck_dim, 1, bias=c.bB, pad_left=0, pad_right=0, mode=1)
-        elif c.modeB == 1 and sub == 1 and not need_z and lay.bottleneck_dim % 16 == 0 and c.modeA == 1:
-            # f32 input (the first layer: features), bottleneck still handed on as planes: linearA runs on the GEMM kernels
-            t_q = x.shape[2] - (ctx - 1)
-            zs = ops.split_like(B, lay.bottleneck_dim, t_q, x.device)
-            z = ops.conv1d(x, c.wB, lay.bottleneck_dim, ctx, bias=c.bB, pad_left=0, pad_right=0, mode=1, y_split=zs, y_split_slope=1.0, no_y=True)
+        def planned(pairs, to_bottleneck=False, planes=False):
+            layers, caches = [m for m, _ in pairs], [c for _, c in pairs]
+            return list(zip(layers, caches, plan_layers(layers, caches, self.tdnnf_planes_only, to_bottleneck, planes)))
+        stack = list(zip(self._stack_layers(), self._cache))
+        if through:
+            after = planned(self._cache_full["after"])          # (planes do not survive pad_replicate: both lists start from f32)
+            hands_planes = bool(after) and after[-1][2].planes_out
+            run = {"stack": planned(stack), "after": after,
+                   "prefinal": [planned([head], planes=hands_planes) for head in self._cache_full["prefinal"]]}
         else:
-            z = ops.conv1d(x, c.wB, lay.bottleneck_dim, ctx, bias=c.bB, stride=sub, pad_left=0, pad_right=0, mode=c.modeB,
-                           x_split=xs if planes_in else None)
-        aux = None
-        if c.codebook is not None:
-            # up to 64 codes the whole codebook sits in LDS (vq_kernel: the served 48 / 64-code tags keep their kernel and their bits);
-            # above, it is walked in tiles (vq_tiled_kernel: the 256-code tag)
-            vq = ops.vq if c.codebook.shape[0] <= 64 else ops.vq_tiled
-            zq, idx, dist = vq(z, c.codebook, want_dist=want_aux, tie=None if tie is None else (tie.pair, tie.scale, tie.counts))
-            if tie is not None:
-                tie.idx = idx
-            aux = (z, idx, dist)
-            z = zq
-        if return_bottleneck:
-            return (z, aux) if want_aux else z
-        kw = {}
-        if lay.use_bypass:
-            lidx = ctx // 2 if ctx > 1 else 0
-            if ctx == 2:
-                lidx = 1
-            kw = dict(res=x, res_scale=lay.bypass_scale, res_toff=lidx, res_tstride=sub)
-        ys = None
-        if c.modeA == 1 and lay.out_dim % 16 == 0:
-            ys = ops.split_like(B, lay.out_dim, z.shape[2], x.device)
-        y = ops.conv1d(z, c.wA, lay.out_dim, 1, bias=c.bA, ch_scale=c.scale, ch_shift=c.shift, relu=True, mode=c.modeA,
-                       x_split=zs, y_split=ys, y_split_slope=1.0, **kw)
-        return y, ys
+            run = planned(stack, to_bottleneck=True)
+        if len(memo) >= 8:              # two precisions x planes_only x two kinds are live: more means replaced weights, let go
+            memo.clear()
+        memo[key] = (self._cache, run)
+        return run
+
+    def _run_layers(self, run, x, xs=None, row_frames=None, tie=None, want_aux=False):
+        """The one layer loop: x [B, feat, T] (xs: its split planes, csrc/conv_f16x3.hip, or None) through the planned layers `run`
+        (`_planned`) -> (y [B, out, T'], planes of y or None); a run that ends at a bottleneck returns that instead: z [B, bott, T'], or
+        (z, (z before the quantiser, indices, distances) or None) with want_aux.  In split-f16 mode the layers hand their activations
+        on as planes as well: linearB stages its 1024 x 3 input with 16-byte copies, linearA reads the bottleneck from planes.
+        row_frames: the frames of each row that are its own (ragged batches: the 1.5x layer's bypass depends on them); tie: the
+        `_TieCtx` of a guarded run."""
+        for lay, c, p in run:
+            ctx, sub, bott, out = lay.context_len, int(lay.subsampling_factor), lay.bottleneck_dim, lay.out_dim
+            B, dev = x.shape[0], x.device
+            if p.form == ONE_CALL:
+                # linearB, linearA with bypass + BatchNorm + ReLU behind one descriptor; on split planes the bottleneck exists only as planes
+                t_q = x.shape[2] - (ctx - 1)
+                zs = ops.split_like(B, bott, t_q, dev) if p.z_planes else None
+                ys = ops.split_like(B, out, t_q, dev) if p.planes_out else None
+                x = ops.tdnnf_layer(x, c.wB, c.bB, c.wA, c.bA, bott, out, ctx, bn_scale=c.scale, bn_shift=c.shift,
+                                    bypass_scale=float(lay.bypass_scale) if lay.use_bypass else 0.0, mode=c.modeB,
+                                    x_split=xs if p.planes_in else None, y_split=ys, z_split=zs, no_y=p.skip_f32, bypass_from_planes=p.x_unwritten)
+            else:
+                zs, res = None, dict(res=x, res_scale=lay.bypass_scale, res_toff=ctx // 2, res_tstride=sub)      # bypass: +0.66 x[:, l:r:sub]
+                if p.form == UNFOLD15:
+                    win, byp = ops.tdnnf_unfold15(x)
+                    if row_frames is not None:
+                        # ragged rows: the reference's bypass of this layer takes int(T / 1.5) frames and zero-fills the rest of
+                        # the windows (chain/nn.py:294-304) — T being the row's OWN frame count, not the padded batch's
+                        for i, n in enumerate(row_frames):
+                            byp[i, :, int(n / 1.5):] = 0
+                    z = ops.conv1d(win, c.wB, bott, 1, bias=c.bB, pad_left=0, pad_right=0, mode=c.modeB)
+                    res = dict(res=byp, res_scale=lay.bypass_scale)
+                elif p.form == SUB_PLANES:
+                    # (the GEMM kernels read the planes the previous layer wrote: 8 x fewer bytes than a strided f32 copy of x)
+                    z = ops.conv1d(x, c.wB, bott, 1, bias=c.bB, pad_left=0, pad_right=0, mode=1, x_split=xs)[:, :, ::sub].contiguous()
+                    zs = ops.act_split(z, 1.0)
+                elif p.form == SUB_GATHER:
+                    z = ops.conv1d(x[:, :, ::sub].contiguous(), c.wB, bott, 1, bias=c.bB, pad_left=0, pad_right=0, mode=1)
+                else:
+                    z = ops.conv1d(x, c.wB, bott, ctx, bias=c.bB, stride=sub, pad_left=0, pad_right=0, mode=c.modeB,
+                                   x_split=xs if p.planes_in else None)
+                aux = None
+                if c.codebook is not None:
+                    # up to 64 codes the whole codebook sits in LDS (vq_kernel: the served 48 / 64-code tags keep their kernel and their
+                    # bits); above, it is walked in tiles (vq_tiled_kernel: the 256-code tag)
+                    vq = ops.vq if c.codebook.shape[0] <= 64 else ops.vq_tiled
+                    zq, idx, dist = vq(z, c.codebook, want_dist=want_aux, tie=None if tie is None else (tie.pair, tie.scale, tie.counts))
+                    if tie is not None:
+                        tie.idx = idx
+                    aux, z = (z, idx, dist), zq
+                if p.bottleneck_only:
+                    return (z, aux) if want_aux else z
+                ys = ops.split_like(B, out, z.shape[2], dev) if p.planes_out else None
+                x = ops.conv1d(z, c.wA, out, 1, bias=c.bA, ch_scale=c.scale, ch_shift=c.shift, relu=True, mode=c.modeA,
+                               x_split=zs, y_split=ys, y_split_slope=1.0, **(res if lay.use_bypass else {}))
+            xs = ys
+            if row_frames is not None:
+                row_frames = [self._layers_out_len([lay], n) for n in row_frames]
+        return x, xs
 
     def _has_vq(self):
         """does the bottleneck layer hold a quantiser?  (tdnnf_vq.py / tdnnf_wav2vec2_vq.py: yes; tdnnf.py / tdnnf_wav2vec2.py, the
@@ -466,31 +509,28 @@ class _TdnnfBase(nn.Module):
         """`vq_flip_stats` of this extractor as configured against its exact-f32 kernels on `wav` [N, n] (device tensor; left
         untouched): how many VQ indices the split-f16 arithmetic decides differently, and whether every one of them is a near-tie."""
         self._need_vq("vq_flip_report")
-        keys = [k for k in ("precision", "w2v2_precision") if hasattr(self, k)]
-        cfg = {k: getattr(self, k) for k in keys}
         _, (z, idx, _) = self.extract_bn(wav.clone(), want_aux=True)
-        try:
-            for k in keys:
-                setattr(self, k, "f32")
+        with self._exact(self):                          # every attribute of `_precision_keys()` at "f32"
             _, (z32, idx32, d32) = self.extract_bn(wav.clone(), want_aux=True)
-        finally:
-            for k, v in cfg.items():
-                setattr(self, k, v)
         return vq_flip_stats(z, idx, z32, idx32, d32)
 
     def _run_stack(self, x, want_aux=False, tie=None):
         """x [B, C, T] (already padded) through tdnn1, tdnnfs[:-2], and the bottleneck of tdnnfs[-2]"""
         self._prepare(x.device)
-        layers = self._stack_layers()
-        xs, valid = None, True
-        for i, (lay, c) in enumerate(zip(layers[:-1], self._cache[:-1])):
-            # a layer whose successor reads its input from planes alone writes no f32 output; its successor then rebuilds the bypass from planes
-            nxt, cn = layers[i + 1], self._cache[i + 1]
-            skip = (self.tdnnf_planes_only and self._plain_on_planes(lay, c, x.shape[1]) and (xs is not None or not lay.use_bypass) and
-                    self._takes_planes(nxt, cn, lay.out_dim, need_z=i + 2 == len(layers)))
-            x, xs = self._tdnnf_layer(lay, c, x, xs, skip_f32=skip, x_valid=valid)
-            valid = not skip
-        return self._tdnnf_layer(layers[-1], self._cache[-1], x, xs, return_bottleneck=True, want_aux=want_aux, tie=tie, x_valid=valid)
+        return self._run_layers(self._planned(False), x, tie=tie, want_aux=want_aux)
+
+    def _bn_guarded(self, feats, wav, defer_ties=False):
+        """stack + VQ with the near-tie guard: -> bn [N, T', D], or (bn, fix) with `fix()` -> rows decided again (the caller runs it
+        once the rest of its launches are enqueued, and repeats what it derived from those rows of bn)"""
+        out, status = self._run_stack_guarded(feats)
+        bn = out.permute(0, 2, 1)
+        if self._has_vq():
+            st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
+            st["utterances"] += bn.shape[0] if status is not None else 0
+        if defer_ties:
+            return bn, (TieFix(self, status, bn, feats, wav) if status is not None else None)
+        self.resolve_ties(status, bn, feats, wav)
+        return bn
 
     # ---- exact VQ indices in the default arithmetic: near-ties counted on the device, their utterances decided again ----------
     def _precision_keys(self):
@@ -643,22 +683,23 @@ class _TdnnfBase(nn.Module):
 
     def _asr_outputs(self, x):
         """x [B, C, T] (features, padded) -> (chain_out, log_softmax(xent_out)) as [B, T', output_dim] views"""
-        full = self._prepare_full(x.device)
-        layers = self._stack_layers()
-        xs = None
-        for lay, c in zip(layers, self._cache):          # the VQ layer runs through (quantised bottleneck -> linearA, BN, ReLU)
-            x, xs = self._tdnnf_layer(lay, c, x, xs)
+        self._prepare_full(x.device)
+        run = self._planned(True)
+        x, _ = self._run_layers(run["stack"], x)         # the VQ layer runs through (quantised bottleneck -> linearA, BN, ReLU)
         x = ops.pad_replicate(x, self.padding_after, self.padding_after, interleave_right=True)
-        xs = None
-        for lay, c in full["after"]:
-            x, xs = self._tdnnf_layer(lay, c, x, xs)
-        outs = []
-        for (lay, c), (w, b, odim) in zip(full["prefinal"], full["out"]):
-            h, hs = self._tdnnf_layer(lay, c, x, xs)
-            outs.append(ops.conv1d(h, w, odim, 1, bias=b, mode=c.modeA, x_split=hs))
-        ops.log_softmax_channels_(outs[1])
-        return outs[0].permute(0, 2, 1), outs[1].permute(0, 2, 1)
+        chain, xent = self._asr_head(run, x)
+        return chain.permute(0, 2, 1), xent.permute(0, 2, 1)
 
+    def _asr_head(self, run, x, row_frames=None):
+        """x [B, C, T] (the stack's output, padded) through tdnnfs_after, the two prefinal layers and their output affines
+        -> (chain_out, log_softmax(xent_out)) as [B, output_dim, T']"""
+        x, xs = self._run_layers(run["after"], x, row_frames=row_frames)
+        outs = []
+        for head, (w, b, odim) in zip(run["prefinal"], self._cache_full["out"]):
+            h, hs = self._run_layers(head, x, xs)
+            outs.append(ops.conv1d(h, w, odim, 1, bias=b, mode=head[0][1].modeA, x_split=hs))
+        ops.log_softmax_channels_(outs[1])
+        return outs
 
     # ---- batched ASR forward of utterances of different lengths --------------------------------------------------
     @staticmethod
@@ -694,29 +735,17 @@ class _TdnnfBase(nn.Module):
         x = torch.zeros(B, feats[0].shape[1], max(L0), dtype=torch.float32, device=dev)
         for i, f in enumerate(feats):
             x[i, :, :L0[i]] = f[0]
-        full = self._prepare_full(dev)
-        layers = self._stack_layers()
-        xs = None
-        for lay, c in zip(layers, self._cache):
-            x, xs = self._tdnnf_layer(lay, c, x, xs)
-        T1 = [self._layers_out_len(layers, n) for n in L0]
+        self._prepare_full(dev)
+        run = self._planned(True)
+        x, _ = self._run_layers(run["stack"], x)
+        T1 = [self._layers_out_len(self._stack_layers(), n) for n in L0]
         pa = self.padding_after
         x2 = torch.zeros(B, x.shape[1], max(T1) + 2 * pa, dtype=torch.float32, device=dev)
         for i in range(B):
             x2[i, :, :T1[i] + 2 * pa] = ops.pad_replicate(x[i:i + 1, :, :T1[i]].contiguous(), pa, pa, interleave_right=True)[0]
-        x, xs = x2, None
-        cur = [n + 2 * pa for n in T1]
-        for lay, c in full["after"]:
-            x, xs = self._tdnnf_layer(lay, c, x, xs, row_frames=cur)
-            cur = [self._layers_out_len([lay], n) for n in cur]
-        T2 = cur
-        outs = []
-        for (lay, c), (w, b, odim) in zip(full["prefinal"], full["out"]):
-            h, hs = self._tdnnf_layer(lay, c, x, xs)
-            outs.append(ops.conv1d(h, w, odim, 1, bias=b, mode=c.modeA, x_split=hs))
-        ops.log_softmax_channels_(outs[1])
-        return [(outs[0][i, :, :T2[i]].t(), outs[1][i, :, :T2[i]].t()) for i in range(B)]
-
+        chain, xent = self._asr_head(run, x2, row_frames=[n + 2 * pa for n in T1])
+        T2 = [self._layers_out_len([lay for lay, _, _ in run["after"]], n + 2 * pa) for n in T1]
+        return [(chain[i, :, :T2[i]].t(), xent[i, :, :T2[i]].t()) for i in range(B)]
 
 class _AsrHead(nn.Module):
     """the ASR output half of the reference nets (tdnnfs_after, prefinal_*, *_output): out of
@@ -757,12 +786,8 @@ class TdnnfVqNet(_TdnnfBase):
     def _fbank_tables(self, device):
         if self._tables is None or self._tables[0].device != device:
             mel = mel_banks(self.input_dim)
-            nz = mel > 0
-            lo = torch.where(nz.any(1), nz.float().argmax(1), torch.zeros(mel.shape[0], dtype=torch.long))
-            hi = mel.shape[1] - torch.flip(nz, [1]).float().argmax(1)
-            hi = torch.where(nz.any(1), hi, torch.zeros_like(hi))
-            self._tables = (povey_window().to(device), mel.to(device), lo.to(torch.int32).to(device),
-                            hi.to(torch.int32).to(device))
+            lo, hi = ops.mel_filter_ranges(mel)
+            self._tables = (povey_window().to(device), mel.to(device), lo.to(device), hi.to(device))
         return self._tables
 
     def features(self, x, scale=1.0):
@@ -783,19 +808,6 @@ class TdnnfVqNet(_TdnnfBase):
             raise _lib.SatError("extract_bn expects a 2-dimensional tensor [N, samples] on the HIP device")
         with self._lock():
             return self._bn_guarded(self.features(x.to(torch.float32).contiguous(), scale=32768.0), x, defer_ties)
-
-    def _bn_guarded(self, feats, wav, defer_ties=False):
-        """stack + VQ with the near-tie guard: -> bn [N, T', D], or (bn, fix) with `fix()` -> rows decided again (the caller runs it
-        once the rest of its launches are enqueued, and repeats what it derived from those rows of bn)"""
-        out, status = self._run_stack_guarded(feats)
-        bn = out.permute(0, 2, 1)
-        if self._has_vq():
-            st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
-            st["utterances"] += bn.shape[0] if status is not None else 0
-        if defer_ties:
-            return bn, (TieFix(self, status, bn, feats, wav) if status is not None else None)
-        self.resolve_ties(status, bn, feats, wav)
-        return bn
 
     def extract_bn(self, x: torch.Tensor, want_aux=False) -> torch.Tensor:
         """inputs [N, n] -> [N, T, 256]   (tdnnf_vq.py:236-257; like the reference this scales

@@ -389,19 +389,6 @@ class TdnnfWav2vec2VqNet(_TdnnfBase):
         with self._lock():
             return self._bn_guarded(self.features(x), x, defer_ties)            # this tag never mutates its input
 
-    def _bn_guarded(self, feats, wav, defer_ties=False):
-        """stack + VQ with the near-tie guard (asrbn.TdnnfVqNet._bn_guarded)"""
-        out, status = self._run_stack_guarded(feats)
-        bn = out.permute(0, 2, 1)
-        if self._has_vq():
-            st = self.__dict__.setdefault("tie_stats", {"utterances": 0, "rerun": 0, "changed": 0})
-            st["utterances"] += bn.shape[0] if status is not None else 0
-        if defer_ties:
-            from .asrbn import TieFix
-            return bn, (TieFix(self, status, bn, feats, wav) if status is not None else None)
-        self.resolve_ties(status, bn, feats, wav)
-        return bn
-
     def _features_of(self, x):
         return self.features(x)
 

@@ -25,33 +25,16 @@ def timed(f, n=10):
 
 feats = bx.features((wav * 32768))
 full = bx._prepare_full(feats.device)
-layers = bx._stack_layers()
+run = bx._planned(True)
 
-
-def stack(x):
-    xs = None
-    for lay, c in zip(layers, bx._cache):
-        x, xs = bx._tdnnf_layer(lay, c, x, xs)
-    return x
-
-
-x = stack(feats)
-print("stack incl. VQ layer  %.3f ms" % timed(lambda: stack(feats)))
+x, _ = bx._run_layers(run["stack"], feats)
+print("stack incl. VQ layer  %.3f ms" % timed(lambda: bx._run_layers(run["stack"], feats)))
 xp = ops.pad_replicate(x, 4, 4, interleave_right=True)
-
-
-def after(x):
-    xs = None
-    for lay, c in full["after"]:
-        x, xs = bx._tdnnf_layer(lay, c, x, xs)
-    return x, xs
-
-
-xa, xas = after(xp)
-print("tdnnfs_after  %.3f ms" % timed(lambda: after(xp)), xa.shape)
-(lay, c), (w, b, odim) = full["prefinal"][0], full["out"][0]
-h, _ = bx._tdnnf_layer(lay, c, xa, xas)
-print("prefinal  %.3f ms" % timed(lambda: bx._tdnnf_layer(lay, c, xa, xas)))
+xa, xas = bx._run_layers(run["after"], xp)
+print("tdnnfs_after  %.3f ms" % timed(lambda: bx._run_layers(run["after"], xp)), xa.shape)
+w, b, odim = full["out"][0]
+h, _ = bx._run_layers(run["prefinal"][0], xa, xas)
+print("prefinal  %.3f ms" % timed(lambda: bx._run_layers(run["prefinal"][0], xa, xas)))
 y = ops.conv1d(h, w, odim, 1, bias=b)
 print("output affine  %.3f ms" % timed(lambda: ops.conv1d(h, w, odim, 1, bias=b)))
 print("log_softmax  %.3f ms" % timed(lambda: ops.log_softmax_channels_(y)))

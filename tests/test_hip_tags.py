@@ -113,15 +113,16 @@ def test_extract_bn_without_a_quantiser_matches_reference_and_oracle(aug, aug_st
 
 def test_bottleneck_without_a_quantiser_is_read_from_planes_only(aug):
     """split-f16 mode: the layer below the bottleneck writes no f32 output and the bottleneck's linearB runs as its own conv on the
-    planes (`_takes_planes(..., need_z=True)`) — no launch more than the VQ tag makes before its quantiser, and the result within
+    planes (its plan record: `reads_f32` False) — no launch more than the VQ tag makes before its quantiser, and the result within
     the split-f16 error of the f32 hand-over"""
     from satools_amd import synthetic
     ext = aug.bn_extractor
     layers = ext._stack_layers()
     ext._prepare(torch.device(DEV))
     assert ext.precision == "f16x3" and ext.tdnnf_planes_only
-    assert ext._takes_planes(layers[-1], ext._cache[-1], layers[-2].out_dim, need_z=True)
-    assert ext._plain_on_planes(layers[-2], ext._cache[-2], 1024)
+    plan = [p for _, _, p in ext._planned(False)]
+    assert len(plan) == len(layers) and plan[-1].bottleneck_only and plan[-1].planes_in and not plan[-1].reads_f32
+    assert plan[-2].form == "one_call" and plan[-2].planes_in and plan[-2].z_planes and plan[-2].planes_out and plan[-2].skip_f32
     wav = synthetic.harm_batch([3, 4, 5], 80000).to(DEV)
     keep = ext.tdnnf_planes_only
     try:
