@@ -429,13 +429,16 @@ class _TdnnfBase(nn.Module):
         memo[key] = (self._cache, run)
         return run
 
-    def _run_layers(self, run, x, xs=None, row_frames=None, tie=None, want_aux=False):
+    def _run_layers(self, run, x, xs=None, row_frames=None, tie=None, want_aux=False, hook=None):
         """The one layer loop: x [B, feat, T] (xs: its split planes, csrc/conv_f16x3.hip, or None) through the planned layers `run`
         (`_planned`) -> (y [B, out, T'], planes of y or None); a run that ends at a bottleneck returns that instead: z [B, bott, T'], or
         (z, (z before the quantiser, indices, distances) or None) with want_aux.  In split-f16 mode the layers hand their activations
         on as planes as well: linearB stages its 1024 x 3 input with 16-byte copies, linearA reads the bottleneck from planes.
         row_frames: the frames of each row that are its own (ragged batches: the 1.5x layer's bypass depends on them); tie: the
-        `_TieCtx` of a guarded run."""
+        `_TieCtx` of a guarded run.  hook: an optional callable that sees (layer name, form, x) after each layer, x the layer's f32
+        output (at a bottleneck end: the bottleneck as returned) — tests; meaningful only with `tdnnf_planes_only` off, where every f32
+        tensor is written (with it on, some are unwritten shape carriers).  None: nothing is launched or waited for on its account."""
+        names = {id(m): n for n, m in self.named_modules()} if hook is not None else None
         for lay, c, p in run:
             ctx, sub, bott, out = lay.context_len, int(lay.subsampling_factor), lay.bottleneck_dim, lay.out_dim
             B, dev = x.shape[0], x.device
@@ -477,11 +480,15 @@ class _TdnnfBase(nn.Module):
                         tie.idx = idx
                     aux, z = (z, idx, dist), zq
                 if p.bottleneck_only:
+                    if hook is not None:
+                        hook(names[id(lay)], p.form, z)
                     return (z, aux) if want_aux else z
                 ys = ops.split_like(B, out, z.shape[2], dev) if p.planes_out else None
                 x = ops.conv1d(z, c.wA, out, 1, bias=c.bA, ch_scale=c.scale, ch_shift=c.shift, relu=True, mode=c.modeA,
                                x_split=zs, y_split=ys, y_split_slope=1.0, **(res if lay.use_bypass else {}))
             xs = ys
+            if hook is not None:
+                hook(names[id(lay)], p.form, x)
             if row_frames is not None:
                 row_frames = [self._layers_out_len([lay], n) for n in row_frames]
         return x, xs
@@ -514,10 +521,10 @@ class _TdnnfBase(nn.Module):
             _, (z32, idx32, d32) = self.extract_bn(wav.clone(), want_aux=True)
         return vq_flip_stats(z, idx, z32, idx32, d32)
 
-    def _run_stack(self, x, want_aux=False, tie=None):
-        """x [B, C, T] (already padded) through tdnn1, tdnnfs[:-2], and the bottleneck of tdnnfs[-2]"""
+    def _run_stack(self, x, want_aux=False, tie=None, hook=None):
+        """x [B, C, T] (already padded) through tdnn1, tdnnfs[:-2], and the bottleneck of tdnnfs[-2]; hook: see `_run_layers`"""
         self._prepare(x.device)
-        return self._run_layers(self._planned(False), x, tie=tie, want_aux=want_aux)
+        return self._run_layers(self._planned(False), x, tie=tie, want_aux=want_aux, hook=hook)
 
     def _bn_guarded(self, feats, wav, defer_ties=False):
         """stack + VQ with the near-tie guard: -> bn [N, T', D], or (bn, fix) with `fix()` -> rows decided again (the caller runs it
@@ -681,22 +688,22 @@ class _TdnnfBase(nn.Module):
             _lib.cache_rebuild_end(device)
         return self._cache_full
 
-    def _asr_outputs(self, x):
-        """x [B, C, T] (features, padded) -> (chain_out, log_softmax(xent_out)) as [B, T', output_dim] views"""
+    def _asr_outputs(self, x, hook=None):
+        """x [B, C, T] (features, padded) -> (chain_out, log_softmax(xent_out)) as [B, T', output_dim] views; hook: see `_run_layers`"""
         self._prepare_full(x.device)
         run = self._planned(True)
-        x, _ = self._run_layers(run["stack"], x)         # the VQ layer runs through (quantised bottleneck -> linearA, BN, ReLU)
+        x, _ = self._run_layers(run["stack"], x, hook=hook)      # the VQ layer runs through (quantised bottleneck -> linearA, BN, ReLU)
         x = ops.pad_replicate(x, self.padding_after, self.padding_after, interleave_right=True)
-        chain, xent = self._asr_head(run, x)
+        chain, xent = self._asr_head(run, x, hook=hook)
         return chain.permute(0, 2, 1), xent.permute(0, 2, 1)
 
-    def _asr_head(self, run, x, row_frames=None):
+    def _asr_head(self, run, x, row_frames=None, hook=None):
         """x [B, C, T] (the stack's output, padded) through tdnnfs_after, the two prefinal layers and their output affines
         -> (chain_out, log_softmax(xent_out)) as [B, output_dim, T']"""
-        x, xs = self._run_layers(run["after"], x, row_frames=row_frames)
+        x, xs = self._run_layers(run["after"], x, row_frames=row_frames, hook=hook)
         outs = []
         for head, (w, b, odim) in zip(run["prefinal"], self._cache_full["out"]):
-            h, hs = self._run_layers(head, x, xs)
+            h, hs = self._run_layers(head, x, xs, hook=hook)
             outs.append(ops.conv1d(h, w, odim, 1, bias=b, mode=head[0][1].modeA, x_split=hs))
         ops.log_softmax_channels_(outs[1])
         return outs

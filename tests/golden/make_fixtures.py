@@ -487,6 +487,68 @@ def main():
             np.savez_compressed(path, **{k: v for k, v in out.items() if part(k) == sfx})
             print("w2v2_lengths:", path, os.path.getsize(path), "bytes")
             assert os.path.getsize(path) < 500_000
+    if want("fbank_lengths"):
+        # the fbank tag on the length catalogue of tests/fbank_lengths.py (the recipe of the "tdnnf" / "asr" / "e2e" sections): per entry the
+        # shapes, the VQ indices, the gap of the two best distances, every 16th dimension of the VQ's input, every 8th fbank bin up to 40 frames;
+        # the head's outputs on the ASR subset; the stack's per-layer activations (every 16th channel) on six entries; convert() with the F0 track
+        # the reference used; the exception type and message where the reference raises
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import fbank_lengths as FL
+        bx = net.bn_extractor
+        out = {}
+        acts = {}
+        mods = [("tdnn1", bx.tdnn1)] + [(f"tdnnfs.{i}", bx.tdnnfs[i]) for i in range(0, 20, 2)]
+        assert [n for n, _ in mods] == FL.LAYER_NAMES
+        hooks = [m.bn.register_forward_hook(lambda mod, i, o, n=n: acts.__setitem__(n, torch.relu(o.detach()).permute(0, 2, 1))) for n, m in mods]
+        hooks.append(bx.tdnnfs[20].tdnn.linearB.register_forward_hook(lambda m, i, o: acts.__setitem__("z", o.detach())))
+        hooks.append(bx.tdnnfs[20].bottleneck_func.quant.register_forward_hook(lambda m, i, o: acts.update(idx=o[5].detach(), dist=o[4].detach())))
+
+        def raised(key, ex):
+            # (the message's last line: above it a TorchScript traceback quotes the reference's source)
+            # (a failure inside a scripted function is a torch.jit.Error whose text names the exception the interpreter met)
+            kind = type(ex).__name__ if type(ex).__module__ == "builtins" else f"{type(ex).__module__}.{type(ex).__name__}"
+            out[key] = np.array([kind, [l for l in str(ex).splitlines() if l.strip()][-1].strip()[:200]])
+            print(f"fbank_lengths: {key}: {type(ex).__name__}: {ex}")
+        with torch.no_grad():
+            for e in FL.ENTRIES:
+                w = e.wav()
+                try:
+                    bn = net.get_bn(w.clone())
+                except Exception as ex:
+                    raised(f"{e.name}/raises", ex)
+                    continue
+                fb = satools.kaldifeat.fbank(w * 32768, num_mel_bins=80, snip_edges=False)
+                out[f"{e.name}/bn_shape"] = np.array(bn.shape, dtype=np.int32)
+                out[f"{e.name}/fbank_shape"] = np.array(fb.shape, dtype=np.int32)
+                out[f"{e.name}/idx"] = acts["idx"].reshape(e.B, -1).numpy().astype(np.int16)
+                srt = acts["dist"].sort(1)[0]
+                out[f"{e.name}/margin"] = (srt[:, 1] - srt[:, 0]).reshape(e.B, -1).numpy()
+                out[f"{e.name}/z_sub"] = acts["z"][..., ::16].numpy()            # [B, T, 16]
+                if e.F <= FL.F_MAX_SMALL:
+                    out[f"{e.name}/fbank_sub"] = fb[..., ::8].numpy()            # [B, F, 10]
+                if e in FL.LAYERS:
+                    for n, _ in mods:
+                        out[f"{e.name}/layer/{n}"] = acts[n][..., ::16].numpy()  # [1, T', 64]
+            for h in hooks:
+                h.remove()
+            for e in FL.ASR:
+                chain, xent = bx(e.wav())
+                out[f"{e.name}/chain_sub"] = chain[..., ::16].numpy()
+                out[f"{e.name}/xent_sub"] = xent[..., ::16].numpy()
+                out[f"{e.name}/xent_lse"] = torch.logsumexp(xent, dim=2).numpy()
+            for name in FL.CONVERT + FL.CONVERT_RAISES:
+                e = FL.BY_NAME[name]
+                try:
+                    f0 = net.get_f0(e.wav())
+                    out[f"{name}/convert"] = net.convert(e.wav(), target=FL.convert_targets(spk, e.B)).numpy()
+                    out[f"{name}/f0"] = f0.numpy()
+                except Exception as ex:
+                    raised(f"{name}/convert_raises", ex)
+        for fname in FL.FIXTURES:
+            path = os.path.join(GOLD, fname)
+            np.savez_compressed(path, **{k: v for k, v in out.items() if FL.fixture_part(k) == fname})
+            print("fbank_lengths:", path, os.path.getsize(path), "bytes")
+            assert os.path.getsize(path) < 500_000
     print("fixtures written to", GOLD)
 
 

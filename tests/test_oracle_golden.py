@@ -127,3 +127,48 @@ def test_mean_reversion_matches_reference(gold):
     import pytest
     with pytest.raises(RuntimeError):
         of0.mean_reversion(torch.zeros(2, 1, 50), 0.5, 32)
+
+
+def test_length_catalogue_matches_reference(gold, fbank_tag_state):
+    """the fbank tag on the length catalogue of tests/fbank_lengths.py (fx_fbank_lengths*.npz: the reference's own Net): up to 40 fbank
+    frames and on the batches the oracle's shapes, fbank bins, pre-quantiser z and every VQ index; the stack's layers on six entries; the
+    head's outputs on the ASR subset.  The GPU sweep (tests/test_hip_fbank_lengths.py) may excuse an index only on a near-tie frame:
+    here, between the reference and its restatement, no index differs at all"""
+    import fbank_lengths as FL
+    state, _ = fbank_tag_state
+    asr, _ = oconv.split_state_dict(state["base_model_state_dict"])
+    fx = FL.fixture(gold)
+    for e in FL.ORACLE_SUBSET:
+        acts, aux = {}, {}
+        bn = otd.extract_bn_fbank(asr, e.wav(), aux=aux, hook=lambda n, t: acts.__setitem__(n, t))
+        assert list(bn.permute(0, 2, 1).shape) == fx[f"{e.name}/bn_shape"].tolist() == [e.B, 256, e.T], e
+        assert list(acts["fbank"].shape) == fx[f"{e.name}/fbank_shape"].tolist(), e
+        assert np.array_equal(aux["idx"].numpy(), fx[f"{e.name}/idx"]), e
+        assert np.abs(aux["z"][..., ::16].numpy() - fx[f"{e.name}/z_sub"]).max() < 5e-5, e
+        if e.F <= FL.F_MAX_SMALL:
+            assert np.abs(acts["fbank"][..., ::8].numpy() - fx[f"{e.name}/fbank_sub"]).max() < 2e-4, e
+        if e in FL.LAYERS:
+            for lay in FL.LAYER_NAMES:
+                assert np.abs(acts[lay][..., ::16].numpy() - fx[f"{e.name}/layer/{lay}"]).max() < 5e-5, (e, lay)
+    for e in FL.ASR:
+        chain, xent = otd.forward_fbank(asr, e.wav())
+        for got, key in ((chain, "chain_sub"), (xent, "xent_sub")):
+            want = fx[f"{e.name}/{key}"]
+            assert got[..., ::16].shape == want.shape, (e, key)
+            assert rms(got.numpy()[..., ::16] - want) <= 1e-5 * max(1.0, rms(want)), (e, key)
+        assert torch.allclose(torch.logsumexp(xent, dim=2), torch.from_numpy(fx[f"{e.name}/xent_lse"]), atol=1e-4), e
+
+
+def test_length_catalogue_vq_indices_on_every_entry(gold, fbank_tag_state):
+    """the oracle's VQ indices equal the reference's on every recorded frame of every entry, the dispatch edges and off-grid lengths too"""
+    import fbank_lengths as FL
+    state, _ = fbank_tag_state
+    asr, _ = oconv.split_state_dict(state["base_model_state_dict"])
+    fx = FL.fixture(gold)
+    for e in FL.RUNNING:
+        if e in FL.ORACLE_SUBSET:
+            continue
+        aux = {}
+        otd.extract_bn_fbank(asr, e.wav(), aux=aux)
+        assert np.array_equal(aux["idx"].numpy(), fx[f"{e.name}/idx"]), e
+        assert np.abs(aux["z"][..., ::16].numpy() - fx[f"{e.name}/z_sub"]).max() < 5e-5, e
