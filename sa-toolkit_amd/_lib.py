@@ -217,6 +217,12 @@ _PROTOS_RAGGED2D16 = {
                                       + [C.c_void_p, C.c_void_p]),
 }
 
+# include/satools_hip_yaapt_long.h (csrc/yaapt_long/): a seventh table, bound like the other six
+_PROTOS_YAAPT_LONG = {
+    "sat_yaapt_long_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "sat_yaapt_long_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -250,6 +256,11 @@ def ragged2d16_symbols():
     return sorted(_PROTOS_RAGGED2D16)
 
 
+def yaapt_long_symbols():
+    """names declared in include/satools_hip_yaapt_long.h that the library must export"""
+    return sorted(_PROTOS_YAAPT_LONG)
+
+
 def library_path():
     """where the in-tree shared library lives (built by sa-toolkit_amd/build.py)"""
     return LIB_PATH
@@ -265,7 +276,7 @@ def lib():
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items())
-                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items())):
+                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items()) + list(_PROTOS_YAAPT_LONG.items())):
             try:
                 fn = getattr(l, name)
             except AttributeError:

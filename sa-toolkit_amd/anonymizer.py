@@ -164,16 +164,17 @@ def build(args):
             # here the whole batch is tracked on the GPU
             from . import f0 as f0_hip
             wav = getattr(wavinfo, "wav", wavinfo).detach()
-            out = f0_hip.yaapt(self._to_device(wav), self.f0_yaapt_opts)
+            out = f0_hip.track(self._to_device(wav), self.f0_yaapt_opts)
             return out.to(wav.device)
 
         def get_f0_ragged(self, wav, lengths):
             """F0 of zero-padded utterances at their own lengths: [B, n_max] + lengths -> [B, T_max] zero-padded,
             on the device — the reference's data loader semantics (bin/pipeline.py:35-41, :52-62: `get_f0` per
-            utterance, tracks zero-padded by the collate) in one launch sequence (sat_yaapt_ragged_f32)."""
+            utterance, tracks zero-padded by the collate) in one launch sequence (sat_yaapt_ragged_f32; sat_yaapt_long_f32 when
+            the longest row has more than 2048 frames: f0.track)."""
             from . import f0 as f0_hip
             xd = self._to_device(wav.detach())
-            return f0_hip.yaapt_ragged(xd, lengths, self.f0_yaapt_opts)
+            return f0_hip.track(xd, self.f0_yaapt_opts, lengths=lengths)
 
         def convert_padded(self, x, lengths, target, defer_status=False):
             """convert() of a zero-padded batch whose F0 tracks are taken per utterance at its own length — the
@@ -193,7 +194,7 @@ def build(args):
                 side = self._f0_stream[cur.cuda_stream] = torch.cuda.Stream(device=xd.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                f0, st = f0_hip.yaapt_ragged(xd, lengths, self.f0_yaapt_opts, defer_status=True)
+                f0, st = f0_hip.track(xd, self.f0_yaapt_opts, lengths=lengths, defer_status=True)
                 f0 = f0.unsqueeze(0)
             xd.record_stream(side)
             bn, fix = self.get_bn(x, defer_ties=True)
@@ -372,7 +373,7 @@ def build(args):
                     side = self._f0_stream[cur.cuda_stream] = torch.cuda.Stream(device=xd.device)
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    f0, self._f0_status = f0_hip.yaapt(xd, self.f0_yaapt_opts, defer_status=True)
+                    f0, self._f0_status = f0_hip.track(xd, self.f0_yaapt_opts, defer_status=True)
                     f0 = f0.unsqueeze(0)
                 xd.record_stream(side)
                 bn, self._bn_fix = self.get_bn(x, defer_ties=True)

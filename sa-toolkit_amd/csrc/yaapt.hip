@@ -17,32 +17,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "yaapt_dev.h"     // the constants and the per-utterance device helpers, shared with csrc/yaapt_long/
 
 namespace sat {
-
-typedef sat_yaapt_plan Plan;
-
-constexpr int FFT_N = 8192;          // fft_length: the real transform whose bins the stages read
-constexpr int FFT_LOG = 12;          // the frames are real: two samples per complex point, FFT_N / 2 points (see the FFT below)
-constexpr int FFT_NP = 1 << FFT_LOG;
-constexpr int MAXP = 4;   // shc_maxpeaks
-constexpr int NC = 6;     // refine candidates: 2 tracks x nccf_maxcands
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int wmin_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // block-wide sum of one float per thread (256 threads), result broadcast; `red` = 8 floats of LDS
 __device__ __forceinline__ float block_sum256(float v, float* red) {
@@ -59,14 +36,6 @@ __device__ __forceinline__ float block_max256(float v, float* red) {
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
-
-// torch.maximum / torch.minimum propagate NaN
-__device__ __forceinline__ float tmax(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
-__device__ __forceinline__ float tmin(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
-
-// ragged batches: U[b] = {samples, padded length L, frames, tda frames} of utterance b (host-computed with the
-// plan's formulas); null = every utterance has the plan's length.  Row strides stay the plan's (the longest).
-__device__ __forceinline__ int ulen(const int* __restrict__ U, int b, int k, int dflt) { return U ? U[b * 4 + k] : dflt; }
 
 // ------------------------------------------------------------------------------------------------
 // prefilter: zero-pad, (square), low-pass biquad -> clamp -> high-pass biquad -> clamp   (yaapt.py:42-51).
@@ -487,7 +456,6 @@ __global__ void __launch_bounds__(256) yaapt_energy_norm_kernel(const float* __r
 // for twice as long, and the FFT blocks leave little room on a CU for the generator's conv blocks of the other job streams.  The FFT
 // kernel ends at the magnitude window (n_mag <= 1280 floats per frame, through the workspace); the tail runs with 6 KB of LDS.
 // Same arithmetic in the same order: the F0 track was unchanged bit for bit by the split.
-constexpr int SPEC_MAGP = 5 * 256;      // floats per frame of the magnitude hand-over (the kernels' 5 x 256 window)
 __global__ void __launch_bounds__(FFT_THREADS) yaapt_spec_kernel(const float* __restrict__ filt, const float* __restrict__ kaiser,
                                                         const float2* __restrict__ tw, const int* __restrict__ vuv,
                                                         float* __restrict__ magbuf, const int* __restrict__ U, const Plan P) {
@@ -611,241 +579,25 @@ __global__ void __launch_bounds__(256) yaapt_spec_peaks_kernel(const float* __re
   for (int i = 0; i < MAXP; ++i) { cp[(size_t)i * nf + f] = pit[i]; cm[(size_t)i * nf + f] = mer[i]; }
 }
 
-// ------------------------------------------------------------------------------------------------
-// per-utterance helpers: ONE wave per utterance, data in LDS, all 64 lanes work (frames are spread
-// over lanes; only the Viterbi recursion itself is sequential in time, and it runs its C x C
-// transitions on C*C lanes).  Callers separate phases with __syncthreads() (a one-wave block).
-// ------------------------------------------------------------------------------------------------
-__device__ float median_small(float* v, int k) {  // k odd, <= 7: middle order statistic
-  for (int i = 1; i < k; ++i) {
-    const float x = v[i];
-    int j = i - 1;
-    while (j >= 0 && v[j] > x) { v[j + 1] = v[j]; --j; }
-    v[j + 1] = x;
-  }
-  return v[k / 2];
-}
-__device__ void medfilt_par(const float* in, float* out, int n, int k) {  // zero-padded sliding median
-  const int pad = k / 2;
-  for (int i = threadIdx.x; i < n; i += 64) {
-    float w[7];
-    for (int j = 0; j < 7; ++j) {
-      const int s = i + j - pad;
-      w[j] = (j < k && s >= 0 && s < n) ? in[s] : 0.f;
-    }
-    out[i] = median_small(w, k);
-  }
-}
-__device__ double wsum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ float mean_par(const float* v, int n) {   // f64 accumulation, rounded once
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += (double)v[i];
-  return (float)(wsum_d(s) / (double)n);   // n == 0 -> NaN like torch.mean of an empty tensor
-}
-__device__ float std_unbiased_par(const float* v, int n) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += (double)v[i];
-  const double m = wsum_d(s) / (double)n;
-  double q = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) { const double d = (double)v[i] - m; q += d * d; }
-  return (float)sqrt(wsum_d(q) / (double)(n - 1));  // n == 1 -> NaN
-}
-
-// path1 (yaapt.py:530-570) on one wave.  local [C][T] (row stride ls), trans(i, j, t) supplied by
-// a functor.  aux[i][j] = PCOST[j] + trans[i][j][t]; K[i] = LAST argmin_j; CCOST[i] = PCOST[K[i]] +
-// trans[K[i]][i][t] + local[i][t]; p_small = LAST argmin_i CCOST.  Back-trace P[t] = PRED[P[t+1]][t+1].
-// Lane (i*C + j) evaluates transition (i, j); lane l < C carries PCOST[l].
-// torch.argmin treats NaN as the smallest value and returns the FIRST one; the reference takes it on the flipped row
-// ("last minimum"), so a NaN cost beats every number and the LAST NaN of a row wins.  NaN costs are real: an utterance
-// whose median-filtered best track is all zero (noise: `rand` inputs) has mean_pitch = mean(empty) = NaN in
-// dynamic() (yaapt.py:326), and every voiced-to-voiced transition cost is NaN.
-__device__ __forceinline__ bool path1_takes(float cand, float best) {
-  return (cand != cand) || (!(best != best) && cand <= best);
-}
-template <int C, class TransFn>
-__device__ void path1_wave(const float* local, int ls, int T, TransFn trans, unsigned char* pred,
-                           unsigned char* path_out) {
-  const int lane = threadIdx.x;
-  const bool act = lane < C * C;
-  const int i = act ? lane / C : 0;
-  const int j = act ? lane % C : 0;
-  float pc = lane < C ? local[lane * ls] : 0.f;
-  for (int t = 1; t < T; ++t) {
-    const float pcj = __shfl(pc, j, 64);
-    const float v = pcj + trans(i, j, t);
-    int K = 0;
-    float bv = __shfl(v, i * C, 64);
-#pragma unroll
-    for (int jj = 1; jj < C; ++jj) {
-      const float vv = __shfl(v, i * C + jj, 64);
-      if (path1_takes(vv, bv)) { bv = vv; K = jj; }   // last minimum wins
-    }
-    const float pcK = __shfl(pc, K, 64);
-    const float cc = (pcK + trans(K, i, t)) + local[i * ls + t];
-    if (act && j == 0) pred[(size_t)i * T + t] = (unsigned char)K;
-    pc = __shfl(cc, (lane * C) & 63, 64);   // lane l < C <- CCOST[l] (held by lane l*C)
-  }
-  __syncthreads();
-  // p_small[T-1] = last argmin_i PCOST (0 when T == 1); every lane computes it from the shuffles
-  int p = 0;
-  {
-    float jv = __shfl(pc, 0, 64);
-#pragma unroll
-    for (int ii = 1; ii < C; ++ii) {
-      const float cv = __shfl(pc, ii, 64);
-      if (path1_takes(cv, jv)) { jv = cv; p = ii; }
-    }
-    if (T <= 1) p = 0;
-  }
-  if (lane == 0) {
-    path_out[T - 1] = (unsigned char)p;
-    for (int t = T - 2; t >= 0; --t) {
-      p = pred[(size_t)p * T + (t + 1)];
-      path_out[t] = (unsigned char)p;
-    }
-  }
-  __syncthreads();
-}
-
-// stable compaction of the frames selected by `flag(f)` (ascending frame order): returns the count,
-// writes the selected frame indices to idx[]
-template <class Pred>
-__device__ int compact_frames(int nf, Pred flag, short* idx) {
-  int base = 0;
-  for (int f0 = 0; f0 < nf; f0 += 64) {
-    const int f = f0 + threadIdx.x;
-    const bool on = f < nf && flag(f);
-    const unsigned long long mask = __ballot(on);
-    if (on) idx[base + __popcll(mask & ((1ull << threadIdx.x) - 1ull))] = (short)f;
-    base += __popcll(mask);
-  }
-  return base;
-}
+// (the per-utterance helpers, median_small .. compact_frames, are in yaapt_dev.h)
 
 // spec_track after the per-frame candidates: selection, smoothing, Viterbi, interpolation.
 // LDS (floats): vcp[4*nf] vcm[4*nf] a[nf] b[nf] spec[nf]; shorts: vidx[nf], index[nf]; bytes pred[4*nf] path[nf]
+// The statements are those of yaapt_spec_select_body.h, which the long form (csrc/yaapt_long/) includes too.
 __global__ void __launch_bounds__(64) yaapt_spec_post_kernel(const float* __restrict__ cand, float* __restrict__ spec_out,
                                                             float* __restrict__ scal, int* __restrict__ status,
                                                             const int* __restrict__ U, const Plan P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int b = blockIdx.x;
-  const int nfs = P.nframes;                      // row stride of the per-frame arrays in global memory
-  const int nf = ulen(U, b, 2, nfs);              // frames of this utterance (also the LDS row pitch)
-  const int lane = threadIdx.x;
-  float* vcp = lds;
-  float* vcm = vcp + 4 * (size_t)nf;
-  float* ta = vcm + 4 * (size_t)nf;
-  float* tb = ta + nf;
-  float* spec = tb + nf;
-  short* vidx = (short*)(spec + nf);
-  short* index = vidx + nf;
-  unsigned char* pred = (unsigned char*)(index + nf);
-  unsigned char* path = pred + 4 * (size_t)nf;
-  const float* cp = cand + (size_t)b * 8 * nfs;
-  const float* cm = cp + 4 * (size_t)nfs;
-  for (int f = lane; f < nf; f += 64) spec[f] = cp[f];
-  // a shorter utterance of a ragged batch whose last spectral frame ends inside its own padded length: the reference fails on the
-  // negative zero extension (yaapt.py:206-210).  yaapt_run refuses it for the plan's own length; only a kernel sees the others
-  if (U && lane == 0 && P.nframe_size + (nf - 1) * P.frame_jump < U[b * 4 + 1]) atomicMax(&status[b], 3);
-  // ... or whose tda frame count differs from its analysis frame count (yaapt_run refuses that too for the plan's own length: the
-  // NCCF kernel walks the analysis frames and would read frame means that were never written): status 4, a refusal after the fact
-  if (U && lane == 0 && U[b * 4 + 3] != nf) atomicMax(&status[b], 4);
-  if (lane == 0) ((int*)scal)[b * 4 + 1] = 0x7fffffff;   // first frame on which the reference's time_track fails, and how (nccf kernel)
-  const int nv = compact_frames(nf, [&](int f) { return cp[f] > 0.f; }, vidx);
-  __syncthreads();
-  for (int i = lane; i < nv; i += 64) {
-    const int f = vidx[i];
-    for (int c = 0; c < 4; ++c) { vcp[c * nf + i] = cp[(size_t)c * nfs + f]; vcm[c * nf + i] = cm[(size_t)c * nfs + f]; }
-  }
-  __syncthreads();
-  float pitch_avg, pitch_std;
-  if (nv == 0) {
-    // the reference fails here (medfilt of an empty tensor, yaapt.py:257 -> :54-69); report it
-    if (lane == 0) atomicMax(&status[b], 1);
-    pitch_avg = 150.f;
-    pitch_std = NAN;
-  } else {
-    const float avg_v = mean_par(vcp, nv);
-    const float std_v = std_unbiased_par(vcp, nv);
-    const float ref = 0.8f * avg_v;
-    for (int i = lane; i < nv; i += 64) {
-      int bi = 0;
-      float bv = fabsf(vcp[i] - ref) * (3.f - vcm[i]);
-      for (int c = 1; c < 4; ++c) {
-        const float d = fabsf(vcp[c * nf + i] - ref) * (3.f - vcm[c * nf + i]);
-        if (d < bv) { bv = d; bi = c; }   // first minimum
-      }
-      index[i] = (short)bi;
-      ta[i] = vcp[bi * nf + i];
-    }
-    __syncthreads();
-    const int mk = P.median_value - 2 > 1 ? P.median_value - 2 : 1;
-    medfilt_par(ta, tb, nv, mk);
-    __syncthreads();
-    for (int i = lane; i < nv; i += 64) vcp[index[i] * nf + i] = tb[i];
-    __syncthreads();
-    const float k1 = (P.dp5_k1 * std_v) / avg_v;
-    if (nv > 2) {
-      // dynamic5 (yaapt.py:506-523): local = 1 - merit (in place), trans = k1*(0.05*d + d*d), d = |p_j(t) - p_i(t-1)|/f0_min
-      for (int c = 0; c < 4; ++c)
-        for (int i = lane; i < nv; i += 64) vcm[c * nf + i] = 1.f - vcm[c * nf + i];
-      __syncthreads();
-      const float f0min = P.f0_min;
-      auto tr = [&](int i, int j, int t) {
-        const float d = fabsf(vcp[j * nf + t] - vcp[i * nf + (t - 1)]) / f0min;
-        return k1 * (0.05f * d + d * d);
-      };
-      path1_wave<4>(vcm, nf, nv, tr, pred, path);
-      for (int t = lane; t < nv; t += 64) tb[t] = vcp[path[t] * nf + t];
-      __syncthreads();
-      medfilt_par(tb, ta, nv, mk);
-    } else {
-      for (int i = lane; i < nv; i += 64) ta[i] = 150.f;
-    }
-    __syncthreads();
-    pitch_avg = mean_par(ta, nv);
-    pitch_std = tmax(std_unbiased_par(ta, nv), pitch_avg * P.spec_pitch_min_std);
-    for (int i = lane; i < nv; i += 64) spec[vidx[i]] = ta[i];
-  }
-  __syncthreads();
-  if (lane == 0) {
-    if (spec[0] < pitch_avg / 2.f) spec[0] = pitch_avg;
-    if (spec[nf - 1] < pitch_avg / 2.f) spec[nf - 1] = pitch_avg;
-  }
-  __syncthreads();
-  // F.interpolate(non-zero values, size=nf, mode='linear', align_corners=False)
-  const int nz = compact_frames(nf, [&](int f) { return spec[f] != 0.f; }, vidx);
-  __syncthreads();
-  for (int i = lane; i < nz; i += 64) tb[i] = spec[vidx[i]];
-  __syncthreads();
-  if (nz == nf) {
-    for (int f = lane; f < nf; f += 64) ta[f] = tb[f];
-  } else {
-    const float scale = (float)nz / (float)nf;
-    for (int f = lane; f < nf; f += 64) {
-      // torch's CPU kernel contracts both expressions into fused multiply-adds (checked bit for
-      // bit against F.interpolate): src = fma(scale, f + 0.5, -0.5), out = fma(l0, x0, l1*x1)
-      float src = fmaf(scale, (float)f + 0.5f, -0.5f);
-      if (src < 0.f) src = 0.f;
-      int i0 = (int)floorf(src);
-      if (i0 > nz - 1) i0 = nz - 1;
-      float l1 = src - (float)i0;
-      l1 = fminf(fmaxf(l1, 0.f), 1.f);
-      const int i1 = i0 + (i0 < nz - 1 ? 1 : 0);
-      const float l0 = 1.f - l1;
-      ta[f] = fmaf(l0, tb[i0], l1 * tb[i1]);
-    }
-  }
-  __syncthreads();
-  if (lane == 0 && nf >= 4) { ta[0] = ta[2]; ta[1] = ta[3]; }
-  __syncthreads();
-  float* out = spec_out + (size_t)b * nfs;
-  for (int f = lane; f < nf; f += 64) out[f] = ta[f];
-  if (lane == 0) scal[b * 4 + 0] = pitch_std;
+#define YAAPT_ARENA lds
+#define YAAPT_SPEC_PATH1()                                                          \
+  auto tr = [&](int i, int j, int t) {                                              \
+    const float d = fabsf(vcp[j * nf + t] - vcp[i * nf + (t - 1)]) / f0min;         \
+    return k1 * (0.05f * d + d * d);                                                \
+  };                                                                                \
+  path1_wave<4>(vcm, nf, nv, tr, pred, path)
+#include "yaapt_spec_select_body.h"
+#undef YAAPT_SPEC_PATH1
+#undef YAAPT_ARENA
 }
 
 // frame means of time_track's in-place subtraction on overlapping views: frame k's first `ov`
@@ -999,145 +751,58 @@ __global__ void __launch_bounds__(256) yaapt_nccf_kernel(const float* __restrict
 
 // refine + dynamic + path1 -> final pitch.  One wave per utterance; frames spread over lanes.
 // LDS floats: rp[6*nf] rm[6*nf] ta[nf] tb[nf]; bytes pred[6*nf] path[nf]
+// The statements are those of yaapt_refine_body.h, which the long form (csrc/yaapt_long/) includes too.
 __global__ void __launch_bounds__(64) yaapt_refine_dp_kernel(const float* __restrict__ tp, const float* __restrict__ tm,
                                                             const float* __restrict__ spec, const float* __restrict__ energy,
                                                             const int* __restrict__ vuv, float* __restrict__ f0,
                                                             const float* __restrict__ scal, int* __restrict__ status,
                                                             float* __restrict__ refined, const int* __restrict__ U, const Plan P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x;
-  const int nfs = P.nframes;                      // row stride in global memory
-  const int nf = ulen(U, b, 2, nfs);              // frames of this utterance (also the LDS row pitch)
-  if (lane == 0) {                                // the first frame the NCCF kernel could not do, if any: 2 or 3
-    const int key = ((const int*)scal)[b * 4 + 1];
-    if (key != 0x7fffffff) atomicMax(&status[b], key & 3);
-  }
-  float* rp = lds;
-  float* rm = rp + NC * (size_t)nf;
-  float* ta = rm + NC * (size_t)nf;
-  float* en = ta + nf;
-  unsigned char* pred = (unsigned char*)(en + nf);
-  unsigned char* path = pred + NC * (size_t)nf;
-  const float* tp1 = tp + ((size_t)b * 2 + 0) * nfs;
-  const float* tp2 = tp + ((size_t)b * 2 + 1) * nfs;
-  const float* tm1 = tm + ((size_t)b * 2 + 0) * nfs;
-  const float* tm2 = tm + ((size_t)b * 2 + 1) * nfs;
-  const float* sp = spec + (size_t)b * nfs;
-  const int* vv = vuv + (size_t)b * nfs;
-  const int nt = ulen(U, b, 3, P.tda_nframes);
-  // concatenate the two tracks (rows 0 and 3 carry the single NCCF candidate), order by merit
-  // descending with a stable sort (torch CPU argsort keeps equal keys in index order)
-  for (int k = lane; k < nf; k += 64) {
-    en[k] = energy[(size_t)b * nfs + k];
-    float p[NC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, m[NC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (k < nt) { p[0] = tp1[k]; m[0] = tm1[k]; p[3] = tp2[k]; m[3] = tm2[k]; }
-    int ord[NC];
-    for (int i = 0; i < NC; ++i) {
-      int pos = i;
-      // key = -m ascending, NaN last; insertion keeps earlier rows first on ties
-      while (pos > 0) {
-        const float a = m[ord[pos - 1]], c = m[i];
-        const bool a_nan = a != a, c_nan = c != c;
-        const bool c_before_a = c_nan ? false : (a_nan ? true : (c > a));
-        if (!c_before_a) break;
-        ord[pos] = ord[pos - 1];
-        --pos;
-      }
-      ord[pos] = i;
-    }
-    // values: flip(sort ascending) ; NaN (sorted last ascending) comes first after the flip
-    float ms[NC];
-    {
-      float t[NC];
-      for (int i = 0; i < NC; ++i) t[i] = m[i];
-      for (int i = 1; i < NC; ++i) {
-        const float x = t[i];
-        int j = i - 1;
-        while (j >= 0 && ((t[j] != t[j]) ? !(x != x) : (x == x && t[j] > x))) { t[j + 1] = t[j]; --j; }
-        t[j + 1] = x;
-      }
-      for (int i = 0; i < NC; ++i) ms[i] = t[NC - 1 - i];
-    }
-    for (int i = 0; i < NC; ++i) { rp[i * nf + k] = p[ord[i]]; rm[i * nf + k] = ms[i]; }
-  }
-  __syncthreads();
-  // best_pitch = medfilt(time_pitch[0], median_value) * vuv
-  medfilt_par(rp, ta, nf, P.median_value);
-  __syncthreads();
-  const float th2 = P.nlfer_thresh2;
-  double acc = 0.0;
-  int cnt = 0;
-  for (int k = lane; k < nf; k += 64) {
-    const float best = ta[k] * (vv[k] ? 1.f : 0.f);
-    ta[k] = best;
-    if (best > 0.f) { acc += (double)best; ++cnt; }
-    const float e = en[k];
-    const float tp0 = rp[k];
-    const bool i1 = e <= th2;
-    const bool i2 = (e > th2) && (tp0 > 0.f);
-    const bool i3 = (e > th2) && (tp0 <= 0.f);
-    bool mm[NC];
-    for (int r = 0; r < NC; ++r) mm[r] = (r >= 1 && r <= NC - 2) && (rp[r * nf + k] == 0.f) && i2;
-    if (i1) for (int r = 0; r < NC; ++r) { rp[r * nf + k] = 0.f; rm[r * nf + k] = P.merit_pivot; }
-    if (i2) { rp[(NC - 1) * nf + k] = 0.f; rm[(NC - 1) * nf + k] = 1.0f - rm[k]; }
-    for (int r = 0; r < NC; ++r) if (mm[r]) rm[r * nf + k] = 0.f;
-    if (i3) {
-      rp[k] = sp[k];
-      rm[k] = tmin(1.f, e / 2.0f);
-      for (int r = 1; r < NC; ++r) { rp[r * nf + k] = 0.f; rm[r * nf + k] = 1.0f - rm[k]; }
-    }
-    rp[(NC - 2) * nf + k] = best;
-    if (best > 0.f) rm[(NC - 2) * nf + k] = rm[k];
-    else rm[(NC - 2) * nf + k] = 1.0f - tmin(1.f, e / 2.0f);
-    rp[(NC - 3) * nf + k] = sp[k];
-    rm[(NC - 3) * nf + k] = e / 5.0f;
-    // refine()'s result for the tests (f0.workspace_views: "refined" = pitch[6], merit[6]): nothing else shows most of its branches,
-    // the final track picks one row per frame
-    float* rd = refined + (size_t)b * 2 * NC * nfs;
-    for (int r = 0; r < NC; ++r) { rd[(size_t)r * nfs + k] = rp[r * nf + k]; rd[(size_t)(NC + r) * nfs + k] = rm[r * nf + k]; }
-    for (int r = 0; r < NC; ++r) rm[r * nf + k] = 1.f - rm[r * nf + k];   // local cost of dynamic()
-  }
-  // dynamic (yaapt.py:321-370)
-  acc = wsum_d(acc);
-  cnt = (int)wsum((float)cnt);
-  const float mean_pitch = (float)(acc / (double)cnt);
-  __syncthreads();
-  const float w1 = P.dp_w1, w2 = P.dp_w2, w3 = P.dp_w3, w4 = P.dp_w4;
-  auto tr = [&](int i, int j, int t) {
-    const float p1 = rp[j * nf + t], p2 = rp[i * nf + (t - 1)];
-    float v = 1.f;
-    if (p1 > 0.f && p2 > 0.f) v = w1 * (fabsf(p1 - p2) / mean_pitch);
-    else if ((p1 == 0.f && p2 > 0.f) || (p1 > 0.f && p2 == 0.f)) v = w2 * (1.f - tmin(1.f, fabsf(en[t - 1] - en[t])));
-    else if (p1 == 0.f && p2 == 0.f) v = w3;
-    return v / w4;
-  };
-  path1_wave<NC>(rm, nf, nf, tr, pred, path);
-  float* out = f0 + (size_t)b * nfs;
-  for (int k = lane; k < nf; k += 64) out[k] = rp[path[k] * nf + k];
-  for (int k = nf + lane; k < nfs; k += 64) out[k] = 0.f;     // shorter utterance of a ragged batch: zero-padded track
+#define YAAPT_ARENA lds
+#define YAAPT_REFINE_PATH1()                                                                                                      \
+  auto tr = [&](int i, int j, int t) {                                                                                            \
+    const float p1 = rp[j * nf + t], p2 = rp[i * nf + (t - 1)];                                                                   \
+    float v = 1.f;                                                                                                                \
+    if (p1 > 0.f && p2 > 0.f) v = w1 * (fabsf(p1 - p2) / mean_pitch);                                                             \
+    else if ((p1 == 0.f && p2 > 0.f) || (p1 > 0.f && p2 == 0.f)) v = w2 * (1.f - tmin(1.f, fabsf(en[t - 1] - en[t])));            \
+    else if (p1 == 0.f && p2 == 0.f) v = w3;                                                                                      \
+    return v / w4;                                                                                                                \
+  };                                                                                                                              \
+  path1_wave<NC>(rm, nf, nf, tr, pred, path)
+#include "yaapt_refine_body.h"
+#undef YAAPT_REFINE_PATH1
+#undef YAAPT_ARENA
 }
 
-}  // namespace sat
-
-using namespace sat;
-
-static size_t yaapt_ws_floats(const Plan& P, int B) {
+// ---- host side.  The pieces below are what sat_yaapt_long_f32 (csrc/yaapt_long/) calls too: declared in yaapt_dev.h ----
+size_t yaapt_ws_floats(const Plan& P, int B) {
   const size_t nf = P.nframes;
   return (size_t)B * (2 * (size_t)P.Lz + 3 * nf /*e_raw, energy, vuv*/ + 8 * nf /*cand*/ + nf /*spec*/ + 4 /*scal*/ +
                       2 * nf /*fmean*/ + 4 * nf /*tp, tm*/ + 2 * NC * nf /*refined*/ + (size_t)SPEC_MAGP * nf /*magnitude windows*/) + 2 * FFT_N /*staged twiddles*/ + 8 + 64;
 }
 
-extern "C" size_t sat_yaapt_workspace_bytes(const sat_yaapt_plan* plan, int B) {
-  if (!plan || B <= 0) return 0;
-  return align_up(yaapt_ws_floats(*plan, B) * sizeof(float), 256);
+YaaptBuffers yaapt_carve(const Plan& P, int B, void* workspace) {
+  YaaptBuffers W;
+  const size_t nf = P.nframes;
+  float* w = (float*)workspace;
+  W.filt = w;            w += (size_t)B * 2 * P.Lz;
+  W.e_raw = w;           w += (size_t)B * nf;
+  W.energy = w;          w += (size_t)B * nf;
+  W.vuv = (int*)w;       w += (size_t)B * nf;
+  W.cand = w;            w += (size_t)B * 8 * nf;
+  W.spec = w;            w += (size_t)B * nf;
+  W.scal = w;            w += (size_t)B * 4;
+  W.fmean = w;           w += (size_t)B * 2 * nf;
+  W.tp = w;              w += (size_t)B * 2 * nf;
+  W.tm = w;              w += (size_t)B * 2 * nf;
+  W.refined = w;         w += (size_t)B * 2 * NC * nf;
+  W.magbuf = w;          w += (size_t)B * nf * SPEC_MAGP;
+  w += (4 - ((uintptr_t)w / 4) % 4) % 4;                     // 16-byte alignment of the float2 table
+  W.stw = (float2*)w;
+  return W;
 }
 
-static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t* U, float* f0, int32_t* status,
-                     const float* hann, const float* kaiser, const float* twiddle, void* workspace,
-                     size_t workspace_bytes, int B, void* stream) {
-  SAT_REQUIRE(plan && wav && f0 && status && hann && kaiser && twiddle && workspace, "yaapt: null pointer");
-  const Plan& P = *plan;
+int yaapt_check_plan(const Plan& P, int B, bool resident) {
   SAT_REQUIRE(B > 0 && P.n > 0, "yaapt: empty batch");
   SAT_REQUIRE(P.nfft == FFT_N, "yaapt: fft_length %d not supported (8192 only)", P.nfft);
   SAT_REQUIRE(P.maxpeaks == MAXP && P.maxcands * 2 == NC, "yaapt: shc_maxpeaks/nccf_maxcands must be 4/3");
@@ -1155,7 +820,8 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
   SAT_REQUIRE(P.tda_len <= 1024 && P.tda_len > P.frame_jump && P.tda_len - P.frame_jump <= 128,
               "yaapt: tda_frame_length / frame_space combination not supported");
   SAT_REQUIRE(P.median_value >= 1 && P.median_value <= 7 && (P.median_value & 1), "yaapt: median_value must be odd <= 7");
-  SAT_REQUIRE(P.nframes >= 4 && P.nframes <= 2048, "yaapt: %d frames not supported (4..2048, i.e. up to ~40 s)", P.nframes);
+  if (resident)
+    SAT_REQUIRE(P.nframes >= 4 && P.nframes <= YAAPT_MAX_RESIDENT_FRAMES, "yaapt: %d frames not supported (4..2048, i.e. up to ~40 s)", P.nframes);
   SAT_REQUIRE(P.tda_nframes == P.nframes, "yaapt: tda frame count differs from the analysis frame count");
   // frame_space > frame_length: the reference fails on a negative zero extension of spec_track (yaapt.py:206-210)
   SAT_REQUIRE(P.nframe_size + (P.nframes - 1) * P.frame_jump >= P.L,
@@ -1163,24 +829,12 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
               "(the reference fails on the negative zero extension of spec_track)", P.nframe_size + (P.nframes - 1) * P.frame_jump, P.L);
   SAT_REQUIRE(P.L == P.n + 2 * P.pad && P.Lz >= P.L && P.Lz >= P.nframe_size + (P.nframes - 1) * P.frame_jump,
               "yaapt: plan lengths inconsistent (L = n + 2 pad, Lz covers the padded signal and the last spectral frame)");
-  SAT_REQUIRE_WORKSPACE(workspace_bytes >= sat_yaapt_workspace_bytes(plan, B), "yaapt: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t nf = P.nframes;
-  float* w = (float*)workspace;
-  float* filt = w;            w += (size_t)B * 2 * P.Lz;
-  float* e_raw = w;           w += (size_t)B * nf;
-  float* energy = w;          w += (size_t)B * nf;
-  int* vuv = (int*)w;         w += (size_t)B * nf;
-  float* cand = w;            w += (size_t)B * 8 * nf;
-  float* spec = w;            w += (size_t)B * nf;
-  float* scal = w;            w += (size_t)B * 4;
-  float* fmean = w;           w += (size_t)B * 2 * nf;
-  float* tp = w;              w += (size_t)B * 2 * nf;
-  float* tm = w;              w += (size_t)B * 2 * nf;
-  float* refined = w;         w += (size_t)B * 2 * NC * nf;
-  float* magbuf = w;          w += (size_t)B * nf * SPEC_MAGP;
-  w += (4 - ((uintptr_t)w / 4) % 4) % 4;                     // 16-byte alignment of the float2 table
-  float2* stw = (float2*)w;   w += 2 * FFT_N;
+  return SAT_OK;
+}
+
+int yaapt_launch_front(const Plan& P, const float* wav, const int32_t* U, int32_t* status, const float* hann, const float* kaiser,
+                       const float* twiddle, const YaaptBuffers& W, int B, hipStream_t s) {
+  float* filt = W.filt;
   const float2* tw = (const float2*)twiddle;
   SAT_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
 
@@ -1199,25 +853,56 @@ static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t
     SAT_HIP(hipFuncSetAttribute((const void*)yaapt_refine_dp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_done_on_device(attr_done, dev);
   }
-  hipLaunchKernelGGL(yaapt_stage_twiddles_kernel, dim3(FFT_N / 256), dim3(256), 0, s, tw, stw);
+  hipLaunchKernelGGL(yaapt_stage_twiddles_kernel, dim3(FFT_N / 256), dim3(256), 0, s, tw, W.stw);
   SAT_LAUNCH_CHECK("yaapt_stage_twiddles_kernel");
-  hipLaunchKernelGGL(yaapt_nlfer_kernel, dim3(P.nframes, B), dim3(FFT_THREADS), fft_lds, s, filt, hann, stw, e_raw, U, P);
+  hipLaunchKernelGGL(yaapt_nlfer_kernel, dim3(P.nframes, B), dim3(FFT_THREADS), fft_lds, s, filt, hann, W.stw, W.e_raw, U, P);
   SAT_LAUNCH_CHECK("yaapt_nlfer_kernel");
-  hipLaunchKernelGGL(yaapt_energy_norm_kernel, dim3(B), dim3(256), 0, s, e_raw, energy, vuv, U, P);
+  hipLaunchKernelGGL(yaapt_energy_norm_kernel, dim3(B), dim3(256), 0, s, W.e_raw, W.energy, W.vuv, U, P);
   SAT_LAUNCH_CHECK("yaapt_energy_norm_kernel");
-  hipLaunchKernelGGL(yaapt_spec_kernel, dim3(P.nframes, B), dim3(FFT_THREADS), fft_lds, s, filt, kaiser, stw, vuv, magbuf, U, P);
+  hipLaunchKernelGGL(yaapt_spec_kernel, dim3(P.nframes, B), dim3(FFT_THREADS), fft_lds, s, filt, kaiser, W.stw, W.vuv, W.magbuf, U, P);
   SAT_LAUNCH_CHECK("yaapt_spec_kernel");
-  hipLaunchKernelGGL(yaapt_spec_peaks_kernel, dim3(P.nframes, B), dim3(256), 0, s, magbuf, vuv, cand, U, P);
+  hipLaunchKernelGGL(yaapt_spec_peaks_kernel, dim3(P.nframes, B), dim3(256), 0, s, W.magbuf, W.vuv, W.cand, U, P);
   SAT_LAUNCH_CHECK("yaapt_spec_peaks_kernel");
-  const size_t post_lds = (size_t)nf * (4 + 4 + 3) * sizeof(float) + nf * 2 * sizeof(short) + nf * 5;
-  hipLaunchKernelGGL(yaapt_spec_post_kernel, dim3(B), dim3(64), post_lds, s, cand, spec, scal, status, U, P);
-  SAT_LAUNCH_CHECK("yaapt_spec_post_kernel");
-  hipLaunchKernelGGL(yaapt_frame_means_kernel, dim3(B, 2), dim3(256), 0, s, filt, fmean, U, P);
-  SAT_LAUNCH_CHECK("yaapt_frame_means_kernel");
-  hipLaunchKernelGGL(yaapt_nccf_kernel, dim3(P.nframes, 2, B), dim3(256), 0, s, filt, fmean, spec, scal, tp, tm, status, U, P);
+  return SAT_OK;
+}
+
+int yaapt_launch_nccf(const Plan& P, const int32_t* U, int32_t* status, const YaaptBuffers& W, int B, hipStream_t s) {
+  hipLaunchKernelGGL(yaapt_nccf_kernel, dim3(P.nframes, 2, B), dim3(256), 0, s, W.filt, W.fmean, W.spec, W.scal, W.tp, W.tm, status, U, P);
   SAT_LAUNCH_CHECK("yaapt_nccf_kernel");
+  return SAT_OK;
+}
+
+}  // namespace sat
+
+using namespace sat;
+
+extern "C" size_t sat_yaapt_workspace_bytes(const sat_yaapt_plan* plan, int B) {
+  if (!plan || B <= 0) return 0;
+  return align_up(yaapt_ws_floats(*plan, B) * sizeof(float), 256);
+}
+
+static int yaapt_run(const sat_yaapt_plan* plan, const float* wav, const int32_t* U, float* f0, int32_t* status,
+                     const float* hann, const float* kaiser, const float* twiddle, void* workspace,
+                     size_t workspace_bytes, int B, void* stream) {
+  SAT_REQUIRE(plan && wav && f0 && status && hann && kaiser && twiddle && workspace, "yaapt: null pointer");
+  const Plan& P = *plan;
+  const int ok = yaapt_check_plan(P, B, true);
+  if (ok != SAT_OK) return ok;
+  SAT_REQUIRE_WORKSPACE(workspace_bytes >= sat_yaapt_workspace_bytes(plan, B), "yaapt: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nf = P.nframes;
+  const YaaptBuffers W = yaapt_carve(P, B, workspace);
+  const int front = yaapt_launch_front(P, wav, U, status, hann, kaiser, twiddle, W, B, s);
+  if (front != SAT_OK) return front;
+  const size_t post_lds = (size_t)nf * (4 + 4 + 3) * sizeof(float) + nf * 2 * sizeof(short) + nf * 5;
+  hipLaunchKernelGGL(yaapt_spec_post_kernel, dim3(B), dim3(64), post_lds, s, W.cand, W.spec, W.scal, status, U, P);
+  SAT_LAUNCH_CHECK("yaapt_spec_post_kernel");
+  hipLaunchKernelGGL(yaapt_frame_means_kernel, dim3(B, 2), dim3(256), 0, s, W.filt, W.fmean, U, P);
+  SAT_LAUNCH_CHECK("yaapt_frame_means_kernel");
+  const int nccf = yaapt_launch_nccf(P, U, status, W, B, s);
+  if (nccf != SAT_OK) return nccf;
   const size_t dp_lds = (size_t)nf * (2 * NC + 2) * sizeof(float) + nf * (NC + 1);
-  hipLaunchKernelGGL(yaapt_refine_dp_kernel, dim3(B), dim3(64), dp_lds, s, tp, tm, spec, energy, vuv, f0, scal, status, refined, U, P);
+  hipLaunchKernelGGL(yaapt_refine_dp_kernel, dim3(B), dim3(64), dp_lds, s, W.tp, W.tm, W.spec, W.energy, W.vuv, f0, W.scal, status, W.refined, U, P);
   SAT_LAUNCH_CHECK("yaapt_refine_dp_kernel");
   return SAT_OK;
 }

@@ -288,6 +288,92 @@ def yaapt_ragged(wav, lengths, opts, defer_status=False):
     return f0
 
 
+MAX_RESIDENT_FRAMES = 2048      # sat_yaapt_f32 / sat_yaapt_ragged_f32: a block's LDS holds the whole utterance (csrc/yaapt_dev.h)
+LONG_CHUNK_STEP, LONG_DEFAULT_CHUNK, LONG_MAX_CHUNK = 64, 1024, 2048     # include/satools_hip_yaapt_long.h
+
+
+def plan_frames(n, opts):
+    """make_plan(n, opts).nframes from the three options it depends on, in plain Python (the dispatch of `track` runs on every call of
+    the batch job's launching thread; a whole plan costs torch calls).  tests/test_yaapt_long_host.py holds the two against each other."""
+    g = lambda k: opts.get(k, DEFAULTS[k])
+    sr = g("sr")
+    pad = int(g("frame_length") / 1000 * int(sr)) // 2
+    half = int(math.floor(g("frame_length") * sr / 1000)) // 2
+    return len(range(half, n + 2 * pad - half, int(math.floor(g("frame_space") * sr / 1000))))
+
+
+def long_frames_ok(P):
+    """whether sat_yaapt_long_f32 takes the plan's length: the prefilter kernel's 31-bit row offsets (about 26 200 frames at a 20 ms hop)"""
+    return 32 * P.n * 4 < 2 ** 31 and 64 * P.Lz * 4 < 2 ** 31 and P.nframes <= 32767
+
+
+def yaapt_long(wav, opts, lengths=None, chunk_frames=0, defer_status=False, return_aux=False):
+    """`yaapt` (lengths None) and `yaapt_ragged` in one function, for any frame count from 4 up to the prefilter's limit
+    (sat_yaapt_long_f32): the per-utterance stages walk the frames in chunks of `chunk_frames` (0 = the default, else a multiple of 64 up to
+    2048) instead of holding the utterance in one block's LDS.  Same arithmetic in the same order: up to 2048 frames the result has the bits
+    of `yaapt` / `yaapt_ragged`.  return_aux: also the named views of the workspace's head (`workspace_views`)."""
+    if not wav.is_cuda:
+        raise _lib.SatError("yaapt_long runs on the HIP device only (no CPU fallback); move the input to 'cuda'")
+    if wav.dim() != 2:
+        raise _lib.SatError("yaapt_long expects [B, samples]")
+    wav = wav.to(torch.float32).contiguous()
+    B, n_max = wav.shape
+    P = make_plan(n_max, dict(opts))
+    ud, also = None, ()
+    if lengths is not None:
+        lens = [int(v) for v in lengths]
+        if len(lens) != B or max(lens) > n_max or min(lens) <= 0:
+            raise _lib.SatError("yaapt_long: lengths do not fit the batch")
+        dims = [length_dims(P, n) for n in lens]
+        if max(d[2] for d in dims) > P.nframes or max(d[1] for d in dims) > P.Lz:
+            raise _lib.SatError("yaapt_long: an utterance exceeds the batch plan")
+        short = [i for i, d in enumerate(dims) if P.nframe_size + (d[2] - 1) * P.frame_jump < d[1]]
+        if short:      # like make_plan, per utterance: the reference fails on each of them
+            d = dims[short[0]]
+            raise _lib.SatError("yaapt_long: utterance(s) %s: " % short + NEGATIVE_EXTENSION[7:] % (P.nframe_size + (d[2] - 1) * P.frame_jump, d[1]))
+        odd = [i for i, d in enumerate(dims) if d[3] != d[2]]
+        if odd:        # as the entry point requires of a single utterance (tda_frame_length above frame_length, at some lengths)
+            raise _lib.SatError("yaapt_long: utterance(s) %s: tda frame count differs from the analysis frame count" % odd)
+    hann, kaiser, tw = _get_tables(P, wav.device)
+    ws_bytes = lib().sat_yaapt_long_workspace_bytes(C.byref(P), B, int(chunk_frames))
+    if not long_frames_ok(P):
+        ws_bytes = 256          # the entry point refuses the plan by name before it looks at the workspace: nothing that large is allocated
+    ws = torch.empty(max(ws_bytes, 256) // 4, dtype=torch.float32, device=wav.device)
+    f0 = torch.empty(B, P.nframes, dtype=torch.float32, device=wav.device)
+    status = torch.empty(B, dtype=torch.int32, device=wav.device)
+    if lengths is not None:
+        ud_host, ud_row = _pinned_ints.take(4 * B)
+        ud_host.copy_(torch.tensor(dims, dtype=torch.int32).reshape(-1))
+        ud = ud_host.to(wav.device, non_blocking=True).view(B, 4)
+        also = (ud_row,)
+    try:
+        check(lib().sat_yaapt_long_f32(C.byref(P), ptr(wav), ptr(ud), ptr(f0), ptr(status), ptr(hann), ptr(kaiser), ptr(tw), ptr(ws),
+                                       ws_bytes, B, int(chunk_frames), stream()), "sat_yaapt_long_f32")
+    except _lib.SatError:
+        if also:                 # refused before any launch: wait for the table's copy, then its pinned row is free again
+            torch.cuda.current_stream().synchronize()
+            _pinned_ints.give(also[0])
+        raise
+    st = F0Status(status, B, also=also)
+    if defer_status:
+        return f0, st
+    st.check()
+    if return_aux:
+        return f0, workspace_views(ws, P, B)
+    return f0
+
+
+def track(wav, opts, lengths=None, defer_status=False):
+    """the F0 of a batch at any length the device takes: a batch plan of up to MAX_RESIDENT_FRAMES frames goes to `yaapt` (lengths None) or
+    `yaapt_ragged` exactly as before, a longer one to `yaapt_long` (every row of a ragged batch then: the rows' results are the same
+    bits either way).  What Net.get_f0 / get_f0_ragged / convert / convert_padded and the batch job call."""
+    if plan_frames(wav.shape[-1], opts) <= MAX_RESIDENT_FRAMES:
+        if lengths is None:
+            return yaapt(wav, opts, defer_status=defer_status)
+        return yaapt_ragged(wav, lengths, opts, defer_status=defer_status)
+    return yaapt_long(wav, opts, lengths=lengths, defer_status=defer_status)
+
+
 def yaapt(wav, opts, defer_status=False, return_aux=False):
     """wav [B, n] on the HIP device -> F0 [B, nframes] on the same device"""
     if not wav.is_cuda:
