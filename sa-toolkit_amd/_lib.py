@@ -223,6 +223,24 @@ _PROTOS_YAAPT_LONG = {
     "sat_yaapt_long_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
 }
 
+
+class GenInputDesc(C.Structure):
+    """mirror of sat_geninput_desc"""
+    _fields_ = [
+        ("B", C.c_int32), ("C_bn", C.c_int32), ("T", C.c_int32), ("T_f0", C.c_int32),
+        ("S", C.c_int32), ("R", C.c_int32), ("n_stats", C.c_int32), ("n_spk", C.c_int32),
+        ("quant_bins", C.c_int32), ("reserved", C.c_int32),
+        ("bn_bstride", C.c_int64), ("bn_cstride", C.c_int64), ("bn_tstride", C.c_int64),
+        ("bn", C.c_void_p), ("f0", C.c_void_p), ("stats", C.c_void_p), ("slice_stat", C.c_void_p), ("noise", C.c_void_p),
+        ("spk", C.c_void_p), ("x", C.c_void_p), ("f0_norm", C.c_void_p),
+    ]
+
+
+# include/satools_hip_geninput.h (csrc/geninput/): an eighth table, bound like the other seven
+_PROTOS_GENINPUT = {
+    "sat_generator_input_f32": (C.c_int, [C.POINTER(GenInputDesc), C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -261,6 +279,11 @@ def yaapt_long_symbols():
     return sorted(_PROTOS_YAAPT_LONG)
 
 
+def geninput_symbols():
+    """names declared in include/satools_hip_geninput.h that the library must export"""
+    return sorted(_PROTOS_GENINPUT)
+
+
 def library_path():
     """where the in-tree shared library lives (built by sa-toolkit_amd/build.py)"""
     return LIB_PATH
@@ -276,7 +299,7 @@ def lib():
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items())
-                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items()) + list(_PROTOS_YAAPT_LONG.items())):
+                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items()) + list(_PROTOS_YAAPT_LONG.items()) + list(_PROTOS_GENINPUT.items())):
             try:
                 fn = getattr(l, name)
             except AttributeError:

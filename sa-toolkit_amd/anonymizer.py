@@ -214,8 +214,8 @@ def build(args):
             out = y.squeeze(0)
 
             def patch(rows):
-                bn, f0_d, spk, arith = ctx
-                xs = ops.assemble_input(bn[rows].contiguous(), f0_d[rows].reshape(len(rows), -1).contiguous(), spk[rows].contiguous(), spk.shape[1])
+                arith = ctx[-1]
+                xs = self._reassemble(ctx, rows)
                 # in the arithmetic the batch ran: a few rows are too small a batch for the ring kernel's default dispatch and would run
                 # "f16x3" where the batch ran "f16f8r" — a row whose indices did not change then keeps its bits
                 f8 = (arith or "").startswith("f16f8r") and not self.hifigan.force_f8
@@ -233,6 +233,11 @@ def build(args):
                 return out, st
             st.check()
             return out
+
+        def _reassemble(self, ctx, rows):
+            """the generator input of `rows` again, from what _forward kept (bn with the rows the second decision rewrote)"""
+            bn, f0_d, spk, _ = ctx
+            return ops.assemble_input(bn[rows].contiguous(), f0_d[rows].reshape(len(rows), -1).contiguous(), spk[rows].contiguous(), spk.shape[1])
 
         def check_precision(self, wav=None, tol=2e-5, fallback=True):
             """Load-time guard for the split-f16 arithmetic (f32 operands carried as hi + lo f16): run a
@@ -305,10 +310,7 @@ def build(args):
                 if gen.precision != "f32":
                     f0 = self.get_f0(wav).unsqueeze(0)
                     bn = bn32 if bn32 is not None else self.get_bn(wav)
-                    f0n = f0.clone()
-                    ops.f0_norm_transform_(f0n)
-                    spk = F.one_hot(torch.zeros(wav.shape[0], dtype=torch.long), num_classes=len(self.spk))
-                    x = ops.assemble_input(bn, f0n.reshape(wav.shape[0], -1), spk.to(dev, torch.float32).contiguous(), spk.shape[1])
+                    x = self._calibration_input(bn, f0, wav.shape[0], dev)
                     keep = gen.precision
                     final = keep
                     try:
@@ -349,6 +351,14 @@ def build(args):
                 warnings.warn(f"satools_amd: {', '.join(fell)} left the range the split-f16 kernels represent on the calibration "
                               f"utterance ({out}); running on the exact-f32 kernels instead (slower, reference-exact)")
             return out
+
+        def _calibration_input(self, bn, f0, B, dev):
+            """the generator input check_precision runs: the raw track [1, B, T'] normalised, the first speaker as the target
+            (the configs of anonymizer_variants.py assemble theirs through their own path)"""
+            f0n = f0.clone()
+            ops.f0_norm_transform_(f0n)
+            spk = F.one_hot(torch.zeros(B, dtype=torch.long), num_classes=len(self.spk))
+            return ops.assemble_input(bn, f0n.reshape(B, -1), spk.to(dev, torch.float32).contiguous(), spk.shape[1])
 
         def get_spk_id(self, wavinfo, target=None):
             if not target:

@@ -102,6 +102,8 @@ def export_frozen(model, path, exact_extractor=False):
     """model: an anonymizer `Net` on the HIP device (satools_amd.load_model(...).to('cuda')).  Besides the configured packings the
     file holds the near-tie guard's calibration and the exact-f32 packings that decide flagged utterances again: the TDNNF stack's
     always (~24 MB), the wav2vec2 encoder's (~1.2 GB) only with `exact_extractor=True`."""
+    if getattr(type(model), "_config", None):
+        raise _lib.SatError(f"export_frozen: frozen export is not built for the '{type(model)._config}' config (anonymizer_variants.py)")
     gen = model.hifigan
     dev = model._device()
     if dev.type != "cuda":

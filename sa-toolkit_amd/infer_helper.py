@@ -17,6 +17,8 @@ import torch
 
 _CONFIGS = {
     "local/tuning/hifigan.py": "anonymizer",
+    "local/tuning/hifigan_clean.py": "anonymizer_clean",      # per-speaker F0 statistics (anonymizer_variants.py)
+    "local/tuning/hifigan_m2o.py": "anonymizer_m2o",          # many-to-one: no target speaker
     "local/chain/tuning/tdnnf_vq.py": "tdnnf_vq",
     "local/chain/tuning/tdnnf_wav2vec2_vq.py": "tdnnf_wav2vec2_vq",
     "local/chain/tuning/tdnnf.py": "tdnnf",                            # the same stacks without the quantiser (the *_aug tags)
@@ -35,6 +37,9 @@ def _builder(base_model_path):
     if kind == "anonymizer":
         from . import anonymizer
         return anonymizer.build
+    if kind in ("anonymizer_clean", "anonymizer_m2o"):
+        from . import anonymizer_variants
+        return anonymizer_variants.build_clean if kind == "anonymizer_clean" else anonymizer_variants.build_m2o
     if kind == "xvector":
         from . import xvector
         return xvector.build

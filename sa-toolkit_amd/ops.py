@@ -288,6 +288,59 @@ def assemble_input(bn, f0, spk_idx, n_spk):
     return x
 
 
+def generator_input(bn, f0, stats, slice_stat=None, quant_bins=0, noise=None, spk=None, want_norm=True):
+    """sat_generator_input_f32 (include/satools_hip_geninput.h): -> (x [B, C_bn + 1 + n_spk, T], f0_norm or None), one launch.
+    `bn` [B, C_bn, T] f32 with ANY positive strides (the permuted view of an extractor's [B, T, C_bn] goes in as it is); `f0` the raw
+    track, [S, R, T_f0] (or [R, T_f0]: S = 1) with S * R = B, not written; `stats` [n_stats, 2] = {mean, std} on the device;
+    `slice_stat` a HOST sequence of S ints (rows of `stats`) or None = row 0 for every slice — checked here against n_stats, since a
+    wrong entry only makes the kernel skip the slice; `quant_bins` / `noise` ([B, T_f0]) as in sat_f0_apply_f32; `spk` [B, n_spk] f32
+    or None.  `f0_norm` holds the normalised values (zeros kept) before quantisation and noise, shaped like `f0`."""
+    if bn.dtype != torch.float32 or bn.dim() != 3:
+        raise _lib.SatError(f"generator_input: bn must be a float32 [B, C_bn, T] tensor, got {bn.dtype} {tuple(bn.shape)}")
+    f0 = _f32c(f0)
+    f3 = f0.unsqueeze(0) if f0.dim() == 2 else f0
+    if f3.dim() != 3:
+        raise _lib.SatError(f"generator_input: f0 must be [S, R, T_f0] or [R, T_f0], got {tuple(f0.shape)}")
+    B, c_bn, T = bn.shape
+    S, R, t_f0 = f3.shape
+    stats = _f32c(stats)
+    if stats.dim() != 2 or stats.shape[1] != 2:
+        raise _lib.SatError(f"generator_input: stats must be [n_stats, 2], got {tuple(stats.shape)}")
+    n_stats = stats.shape[0]
+    keep = None
+    if slice_stat is not None:
+        host = [int(v) for v in (slice_stat.tolist() if torch.is_tensor(slice_stat) else slice_stat)]
+        if len(host) != S:
+            raise _lib.SatError(f"generator_input: slice_stat has {len(host)} entries for {S} slices")
+        for i, v in enumerate(host):
+            if not 0 <= v < n_stats:
+                raise _lib.SatError(f"generator_input: slice_stat[{i}] = {v} outside 0 .. {n_stats - 1}")
+        keep = torch.tensor(host, dtype=torch.int32).pin_memory().to(bn.device, non_blocking=True)
+    if noise is not None:
+        noise = _f32c(noise)
+        if noise.numel() != B * t_f0:
+            raise _lib.SatError(f"generator_input: noise has {noise.numel()} elements, f0 rows have {B} x {t_f0}")
+    n_spk = 0
+    if spk is not None:
+        spk = _f32c(spk)
+        if spk.dim() != 2 or spk.shape[0] != B:
+            raise _lib.SatError(f"generator_input: spk must be [B, n_spk] with B = {B}, got {tuple(spk.shape)}")
+        n_spk = spk.shape[1]
+        if n_spk == 0:
+            spk = None
+    for t in (f3, stats, noise, spk):
+        if t is not None and t.device != bn.device:
+            raise _lib.SatError("generator_input: every tensor on bn's device")
+    x = torch.empty(B, c_bn + 1 + n_spk, T, dtype=torch.float32, device=bn.device)
+    norm = torch.empty_like(f0) if want_norm else None
+    d = _lib.GenInputDesc(B=B, C_bn=c_bn, T=T, T_f0=t_f0, S=S, R=R, n_stats=n_stats, n_spk=n_spk, quant_bins=int(quant_bins), reserved=0,
+                          bn_bstride=bn.stride(0), bn_cstride=bn.stride(1), bn_tstride=bn.stride(2),
+                          bn=bn.data_ptr() if bn.is_cuda else ptr(bn), f0=ptr(f3), stats=ptr(stats), slice_stat=ptr(keep), noise=ptr(noise),
+                          spk=ptr(spk), x=ptr(x), f0_norm=ptr(norm))
+    check(lib().sat_generator_input_f32(C.byref(d), stream()), "sat_generator_input_f32")
+    return x, norm
+
+
 def pcm16_to_f32(pcm):
     """int16 PCM on the device -> f32 in [-1, 1): s / 32768, what torchaudio.load hands the reference (utils/kaldi.py:113-125)"""
     if pcm.dtype != torch.int16 or not pcm.is_cuda:

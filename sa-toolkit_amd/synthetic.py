@@ -27,6 +27,11 @@ def utt2spk(n=N_SPEAKERS):
 
 def parse_tag(tag):
     tag = re.sub(r"_v\d+$", "", tag)
+    # the reference's experiment-directory names of its two other anonymizer configs (hifigan_clean.py, hifigan_m2o.py)
+    if tag.startswith("clean_hifigan_"):
+        return "anonymizer_clean", tag[len("clean_hifigan_"):]
+    if tag.startswith("hifigan_m2o_"):
+        return "anonymizer_m2o", tag[len("hifigan_m2o_"):]
     if tag.startswith("hifigan_"):
         return "anonymizer", tag[len("hifigan_"):]
     return "asrbn", tag
@@ -144,12 +149,47 @@ _FILLED = {}
 _FILLED_MAX = 1 if os.environ.get("SATOOLS_AMD_SYNTH_CACHE", "1") != "0" else 0
 
 
+_ANONYMIZER_CONFIGS = {"anonymizer": "local/tuning/hifigan.py", "anonymizer_clean": "local/tuning/hifigan_clean.py",
+                       "anonymizer_m2o": "local/tuning/hifigan_m2o.py"}
+
+
+def speaker_cmvn_state(n_spk, seed=0, skip=()):
+    """seeded SpeakerCMVN state of the clean config with computed statistics for every speaker index (but those in `skip`): the
+    accumulators of `frames` voiced F0 values around a speaker's own mean, and the reference's mean / std tensors from them
+    (cmvn.py:323-346: Python-float moments, torch.tensor(mean), sqrt(tensor(var + 1e-6)))"""
+    g = _gen("f0_norm.speaker_stats", seed)
+    mean = 90.0 + 160.0 * torch.rand(n_spk, generator=g, dtype=torch.float64)
+    std = 12.0 + 30.0 * torch.rand(n_spk, generator=g, dtype=torch.float64)
+    frames = torch.randint(2000, 20000, (n_spk,), generator=g)
+    stats, done = {}, {}
+    for i in range(n_spk):
+        n, m, s = int(frames[i]), float(mean[i]), float(std[i])
+        st = {"sum": m * n, "sum_sq": (s * s + m * m) * n, "total_frames": n}
+        done[str(i)] = i not in skip
+        if i not in skip:
+            mu = st["sum"] / n
+            var = st["sum_sq"] / n - mu ** 2
+            st["mean"], st["std"] = torch.tensor(mu), torch.sqrt(torch.tensor(var + 1e-6))
+        stats[str(i)] = st
+    return {"speaker_stats": stats, "stats_computed": done, "computed": True, "keep_zeros": True}
+
+
+def speaker_cmvn_buffer(n_spk, seed=0, size=900000, skip=()):
+    """that state as the reference stores it: pickled into a zero-padded uint8 buffer (`f0_norm.model_state_buffer`)"""
+    import pickle
+    blob = pickle.dumps(speaker_cmvn_state(n_spk, seed, skip))
+    assert len(blob) < size
+    buf = torch.zeros(size, dtype=torch.uint8)
+    buf[:len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
+    return buf
+
+
 def checkpoint(tag, seed=0, conditioning="auto"):
     """a reference-format checkpoint dict for `tag` with synthetic weights"""
     from . import infer_helper
     kind, asr_name = parse_tag(tag)
-    if kind == "anonymizer":
-        state = {"install_path": "", "task_path": "/egs/vc/libritts", "base_model_path": "local/tuning/hifigan.py",
+    if kind in _ANONYMIZER_CONFIGS:
+        state = {"install_path": "", "task_path": "/egs/vc/libritts", "base_model_path": _ANONYMIZER_CONFIGS[kind],
                  "base_model_params": {"utt2spk": utt2spk()},
                  "base_model_args": {"asrbn_model": ASR_DIR.format(name=asr_name), "f0_transformation": ""}}
     else:
@@ -167,6 +207,8 @@ def checkpoint(tag, seed=0, conditioning="auto"):
         sd = fill_state_dict(net.state_dict(), seed)
         if conditioning:
             apply_conditioning(sd, dict(np.load(conditioning)))
+        if kind == "anonymizer_clean":
+            sd["f0_norm.model_state_buffer"] = speaker_cmvn_buffer(len(net.spk), seed, sd["f0_norm.model_state_buffer"].numel())
         if _FILLED_MAX:
             while len(_FILLED) >= _FILLED_MAX:
                 _FILLED.pop(next(iter(_FILLED)))
