@@ -1,4 +1,4 @@
-"""ctypes binding of libsatools_hip.so (include/satools_hip.h).
+"""ctypes binding of libsatools_hip.so (include/satools_hip*.h: one table, COMPONENTS).
 
 The product path has no CPU fallback: if the library is missing or a call fails, an exception
 is raised.  Nothing here imports from `oracle/`."""
@@ -71,159 +71,6 @@ class MrfDesc(C.Structure):
     ]
 
 
-_PROTOS = {
-    "sat_abi_version": (C.c_int, []),
-    "sat_last_error": (C.c_char_p, []),
-    "sat_last_dispatch_name": (C.c_char_p, []),
-    "sat_device_info": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
-    "sat_conv1d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sat_conv1d_multi_f32": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
-    "sat_conv1d_packed_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "sat_convtranspose_phase_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "sat_upsample_grouped_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "sat_convtranspose_zero_taps": (C.c_uint32, [C.c_int, C.c_int, C.c_int]),
-    "sat_hifigan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
-                                     C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "sat_hifigan_num_convs": (C.c_int, [C.c_void_p]),
-    "sat_hifigan_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
-    "sat_hifigan_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "sat_hifigan_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
-                                          C.c_int, C.c_void_p]),
-    "sat_hifigan_destroy": (None, [C.c_void_p]),
-    "sat_hifigan_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
-    "sat_hifigan_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
-    "sat_hifigan_set_range_probe": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "sat_resblock_pair_f16x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "sat_mrf_debug_stamps": (C.c_int, [C.c_void_p]),
-    "sat_attention_debug_stamps": (C.c_int, [C.c_void_p]),
-    "sat_pair32_debug_stamps": (C.c_int, [C.c_void_p]),
-    "sat_convring_debug_stamps": (C.c_int, [C.c_void_p]),
-    "sat_resblock_mrf_supported": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "sat_resblock_mrf_scratch_bytes": (C.c_size_t, [C.c_int, C.POINTER(C.c_int)]),
-    "sat_resblock_mrf_f16x3": (C.c_int, [C.POINTER(MrfDesc), C.c_void_p]),
-    "sat_resblock_pair_scaled_f16x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p]),
-    "sat_hifigan_set_conv_descale": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
-    "sat_hifigan_set_conv_f8r": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "sat_conv1d_f8r_supported": (C.c_int, [C.POINTER(ConvDesc)]),
-    "sat_planes_f8_sidecar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_upsample2_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "sat_upsample2_f16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_int, C.c_int,
-                                      C.c_int, C.c_void_p]),
-    "sat_tdnnf_layer_f32": (C.c_int, [C.POINTER(TdnnfLayerDesc), C.c_void_p]),
-    "sat_act_split_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
-    "sat_hifigan_convpost_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_int, C.c_void_p]),
-    "sat_fbank_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "sat_fbank_cmvn_pad_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
-                                         C.c_int, C.c_void_p]),
-    "sat_vq_argmin_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_vq_argmin_gather_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_vq_argmin_gather_tiled_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                 C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_vq_argmin_gather_tiled_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_pad_replicate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_void_p]),
-    "sat_f0_stats_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "sat_f0_apply_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "sat_f0_mean_reversion_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
-    "sat_yaapt_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "sat_yaapt_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
-    "sat_yaapt_ragged_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
-    "sat_tdnnf_unfold15_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_log_softmax_channels_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_melspec_logmel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                         C.c_int, C.c_float, C.c_void_p]),
-    "sat_instnorm_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
-    "sat_row_mean_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "sat_add3_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_int64] * 8 + [C.c_void_p]),
-    "sat_se_gate_add_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64] * 2 + [C.c_void_p]),
-    "sat_tanh_inplace_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "sat_attentive_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_l2norm_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "sat_w2v2_conv0_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_int, C.c_void_p]),
-    "sat_layernorm_channels_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                             C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
-    "sat_layernorm_channels_planes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
-                                                    C.c_void_p]),
-    "sat_w2v2_conv0_layernorm_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
-    "sat_conv_set_option": (C.c_int, [C.c_char_p, C.c_int]),
-    "sat_clock_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "sat_attention_f16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, C.c_float, C.c_void_p]),
-    "sat_softmax_columns_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
-    "sat_transpose_heads_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p]),
-    "sat_res2_chain_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sat_linear_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p]),
-    "sat_pcm16_to_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
-    "sat_pcm16_from_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
-    "sat_assemble_input_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_void_p]),
-    # ASV evaluation (csrc/asv_score.hip): added under ABI 8, see lib()
-    "sat_cohort_topk_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sat_trial_scores_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int,
-                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sat_segment_mean_l2norm_f32": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_void_p]),
-    # ResNet x-vector extractor (csrc/conv2d.hip): added under ABI 8 likewise
-    "sat_conv2d_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
-    "sat_se_scale_add_relu_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
-    "sat_row_mean_std_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-}
-
-# include/satools_hip_stats.h (csrc/stats/): a second table, bound like the first one
-_PROTOS_STATS = {
-    "sat_eer_bootstrap_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
-}
-
-# include/satools_hip_conv2d16.h (csrc/conv2d16/): a third table, bound like the other two
-_PROTOS_CONV2D16 = {
-    "sat_conv2d_f16x3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
-}
-
-# include/satools_hip_ragged.h (csrc/ragged/): a fourth table, bound like the other three
-_I32P = C.POINTER(C.c_int32)
-_PROTOS_RAGGED = {
-    "sat_melspec_logmel_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, _I32P] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
-    "sat_instnorm_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
-    "sat_row_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
-    "sat_se_gate_add_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_int64, C.c_void_p]),
-    "sat_attentive_stats_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
-    "sat_res2_chain_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 8 + [C.c_void_p]),
-}
-
-# include/satools_hip_ragged2d.h (csrc/ragged2d/): a fifth table, bound like the other four
-_PROTOS_RAGGED2D = {
-    "sat_conv2d_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
-    "sat_plane_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
-    "sat_se_scale_add_relu_segments_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
-    "sat_row_mean_std_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
-}
-
-# include/satools_hip_ragged2d16.h (csrc/ragged2d16/): a sixth table, bound like the other five
-_PROTOS_RAGGED2D16 = {
-    "sat_conv2d_f16x3_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9
-                                      + [C.c_void_p, C.c_void_p]),
-}
-
-# include/satools_hip_yaapt_long.h (csrc/yaapt_long/): a seventh table, bound like the other six
-_PROTOS_YAAPT_LONG = {
-    "sat_yaapt_long_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "sat_yaapt_long_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
-}
-
-
 class GenInputDesc(C.Structure):
     """mirror of sat_geninput_desc"""
     _fields_ = [
@@ -236,52 +83,167 @@ class GenInputDesc(C.Structure):
     ]
 
 
-# include/satools_hip_geninput.h (csrc/geninput/): an eighth table, bound like the other seven
-_PROTOS_GENINPUT = {
-    "sat_generator_input_f32": (C.c_int, [C.POINTER(GenInputDesc), C.c_void_p]),
+_I32P = C.POINTER(C.c_int32)
+
+# One entry per component of the library's C ABI: "core" is csrc/*.hip with include/satools_hip.h, every other name is a directory
+# csrc/<name>/ with include/satools_hip_<name>.h (build.py finds those by the same convention; tests/test_components_host.py holds
+# headers, directories and this mapping against each other, argument by argument).  name -> (restype, argtypes).
+COMPONENTS = {
+    "core": {
+        "sat_abi_version": (C.c_int, []),
+        "sat_last_error": (C.c_char_p, []),
+        "sat_last_dispatch_name": (C.c_char_p, []),
+        "sat_device_info": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
+        "sat_conv1d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sat_conv1d_multi_f32": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+        "sat_conv1d_packed_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sat_convtranspose_phase_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sat_upsample_grouped_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sat_convtranspose_zero_taps": (C.c_uint32, [C.c_int, C.c_int, C.c_int]),
+        "sat_hifigan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sat_hifigan_num_convs": (C.c_int, [C.c_void_p]),
+        "sat_hifigan_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+        "sat_hifigan_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+        "sat_hifigan_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                              C.c_int, C.c_void_p]),
+        "sat_hifigan_destroy": (None, [C.c_void_p]),
+        "sat_hifigan_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+        "sat_hifigan_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
+        "sat_hifigan_set_range_probe": (C.c_int, [C.c_void_p, C.c_void_p]),
+        "sat_resblock_pair_f16x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+        "sat_mrf_debug_stamps": (C.c_int, [C.c_void_p]),
+        "sat_attention_debug_stamps": (C.c_int, [C.c_void_p]),
+        "sat_pair32_debug_stamps": (C.c_int, [C.c_void_p]),
+        "sat_convring_debug_stamps": (C.c_int, [C.c_void_p]),
+        "sat_resblock_mrf_supported": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "sat_resblock_mrf_scratch_bytes": (C.c_size_t, [C.c_int, C.POINTER(C.c_int)]),
+        "sat_resblock_mrf_f16x3": (C.c_int, [C.POINTER(MrfDesc), C.c_void_p]),
+        "sat_resblock_pair_scaled_f16x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+        "sat_hifigan_set_conv_descale": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+        "sat_hifigan_set_conv_f8r": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+        "sat_conv1d_f8r_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+        "sat_planes_f8_sidecar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_upsample2_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sat_upsample2_f16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_int, C.c_int,
+                                          C.c_int, C.c_void_p]),
+        "sat_tdnnf_layer_f32": (C.c_int, [C.POINTER(TdnnfLayerDesc), C.c_void_p]),
+        "sat_act_split_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+        "sat_hifigan_convpost_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_int, C.c_void_p]),
+        "sat_fbank_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+        "sat_fbank_cmvn_pad_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p]),
+        "sat_vq_argmin_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_vq_argmin_gather_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_vq_argmin_gather_tiled_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_vq_argmin_gather_tiled_tie_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_pad_replicate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p]),
+        "sat_f0_stats_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+        "sat_f0_apply_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+        "sat_f0_mean_reversion_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+        "sat_yaapt_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+        "sat_yaapt_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+        "sat_yaapt_ragged_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+        "sat_tdnnf_unfold15_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_log_softmax_channels_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_melspec_logmel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_int, C.c_float, C.c_void_p]),
+        "sat_instnorm_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+        "sat_row_mean_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "sat_add3_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_int64] * 8 + [C.c_void_p]),
+        "sat_se_gate_add_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64] * 2 + [C.c_void_p]),
+        "sat_tanh_inplace_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+        "sat_attentive_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_l2norm_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "sat_w2v2_conv0_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p]),
+        "sat_layernorm_channels_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+        "sat_layernorm_channels_planes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                        C.c_void_p]),
+        "sat_w2v2_conv0_layernorm_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+        "sat_conv_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+        "sat_clock_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "sat_attention_f16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_float, C.c_void_p]),
+        "sat_softmax_columns_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+        "sat_transpose_heads_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p]),
+        "sat_res2_chain_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "sat_linear_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
+        "sat_pcm16_to_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+        "sat_pcm16_from_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+        "sat_assemble_input_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_void_p]),
+        # ASV evaluation (csrc/asv_score.hip): added under ABI 8, see lib()
+        "sat_cohort_topk_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sat_trial_scores_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "sat_segment_mean_l2norm_f32": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_void_p]),
+        # ResNet x-vector extractor (csrc/conv2d.hip): added under ABI 8 likewise
+        "sat_conv2d_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
+        "sat_se_scale_add_relu_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+        "sat_row_mean_std_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    },
+    "stats": {
+        "sat_eer_bootstrap_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    },
+    "conv2d16": {
+        "sat_conv2d_f16x3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    },
+    "ragged": {
+        "sat_melspec_logmel_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, _I32P] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+        "sat_instnorm_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+        "sat_row_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+        "sat_se_gate_add_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_int64, C.c_void_p]),
+        "sat_attentive_stats_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
+        "sat_res2_chain_segments_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 8 + [C.c_void_p]),
+    },
+    "ragged2d": {
+        "sat_conv2d_segments_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
+        "sat_plane_mean_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+        "sat_se_scale_add_relu_segments_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
+        "sat_row_mean_std_segments_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    },
+    "ragged2d16": {
+        "sat_conv2d_f16x3_segments_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9
+                                          + [C.c_void_p, C.c_void_p]),
+    },
+    "yaapt_long": {
+        "sat_yaapt_long_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+        "sat_yaapt_long_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    },
+    "geninput": {
+        "sat_generator_input_f32": (C.c_int, [C.POINTER(GenInputDesc), C.c_void_p]),
+    },
 }
 
 _lib = None
 
 
-def exported_symbols():
-    """names declared in include/satools_hip.h that the library must export"""
-    return sorted(_PROTOS)
+def symbols(component=None):
+    """names the library must export: those of one component, or of all of them"""
+    return sorted(n for c, protos in COMPONENTS.items() if component in (None, c) for n in protos)
 
 
-def stats_symbols():
-    """names declared in include/satools_hip_stats.h that the library must export"""
-    return sorted(_PROTOS_STATS)
-
-
-def conv2d16_symbols():
-    """names declared in include/satools_hip_conv2d16.h that the library must export"""
-    return sorted(_PROTOS_CONV2D16)
-
-
-def ragged_symbols():
-    """names declared in include/satools_hip_ragged.h that the library must export"""
-    return sorted(_PROTOS_RAGGED)
-
-
-def ragged2d_symbols():
-    """names declared in include/satools_hip_ragged2d.h that the library must export"""
-    return sorted(_PROTOS_RAGGED2D)
-
-
-def ragged2d16_symbols():
-    """names declared in include/satools_hip_ragged2d16.h that the library must export"""
-    return sorted(_PROTOS_RAGGED2D16)
-
-
-def yaapt_long_symbols():
-    """names declared in include/satools_hip_yaapt_long.h that the library must export"""
-    return sorted(_PROTOS_YAAPT_LONG)
-
-
-def geninput_symbols():
-    """names declared in include/satools_hip_geninput.h that the library must export"""
-    return sorted(_PROTOS_GENINPUT)
+def header(component):
+    """file name under include/ that declares the component's entry points"""
+    COMPONENTS[component]
+    return "satools_hip.h" if component == "core" else f"satools_hip_{component}.h"
 
 
 def library_path():
@@ -298,8 +260,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python sa-toolkit_amd/build.py` "
                 "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_STATS.items()) + list(_PROTOS_CONV2D16.items()) + list(_PROTOS_RAGGED.items())
-                                  + list(_PROTOS_RAGGED2D.items()) + list(_PROTOS_RAGGED2D16.items()) + list(_PROTOS_YAAPT_LONG.items()) + list(_PROTOS_GENINPUT.items())):
+        for name, (res, args) in [item for protos in COMPONENTS.values() for item in protos.items()]:
             try:
                 fn = getattr(l, name)
             except AttributeError:

@@ -11,33 +11,27 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 
+def components():
+    """names of the components besides the core: a sub-directory csrc/<name>/ with at least one .hip file is one, and its entry
+    points are declared in include/satools_hip_<name>.h (the core is csrc/*.hip with include/satools_hip.h)"""
+    csrc = os.path.join(HERE, "csrc")
+    return sorted(d for d in os.listdir(csrc) if glob.glob(os.path.join(csrc, d, "*.hip")))
+
+
 def sources():
-    """the kernels directly in csrc/ (include/satools_hip.h), those of csrc/stats/ (include/satools_hip_stats.h), those of
-    csrc/conv2d16/ (include/satools_hip_conv2d16.h), those of csrc/ragged/ (include/satools_hip_ragged.h), those of csrc/ragged2d/
-    (include/satools_hip_ragged2d.h), those of csrc/ragged2d16/ (include/satools_hip_ragged2d16.h), those of csrc/yaapt_long/
-    (include/satools_hip_yaapt_long.h) and those of csrc/geninput/ (include/satools_hip_geninput.h): one library"""
-    return (sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip"))) + sorted(glob.glob(os.path.join(HERE, "csrc", "stats", "*.hip")))
-            + sorted(glob.glob(os.path.join(HERE, "csrc", "conv2d16", "*.hip"))) + sorted(glob.glob(os.path.join(HERE, "csrc", "ragged", "*.hip")))
-            + sorted(glob.glob(os.path.join(HERE, "csrc", "ragged2d", "*.hip"))) + sorted(glob.glob(os.path.join(HERE, "csrc", "ragged2d16", "*.hip")))
-            + sorted(glob.glob(os.path.join(HERE, "csrc", "yaapt_long", "*.hip"))) + sorted(glob.glob(os.path.join(HERE, "csrc", "geninput", "*.hip"))))
+    """the kernels of the core, then those of every component, each directory's in sorted order: one library"""
+    csrc = os.path.join(HERE, "csrc")
+    return [s for d in [csrc] + [os.path.join(csrc, c) for c in components()] for s in sorted(glob.glob(os.path.join(d, "*.hip")))]
 
 
 def headers():
-    """what every object depends on besides its own source"""
-    inc = os.path.join(HERE, "..", "include")
-    return (glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "stats", "*.h"))
-            + glob.glob(os.path.join(HERE, "csrc", "conv2d16", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "ragged", "*.h"))
-            + glob.glob(os.path.join(HERE, "csrc", "ragged2d", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "ragged2d16", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "yaapt_long", "*.h"))
-            + glob.glob(os.path.join(HERE, "csrc", "geninput", "*.h"))
-            + [os.path.join(inc, "satools_hip.h"), os.path.join(inc, "satools_hip_stats.h"), os.path.join(inc, "satools_hip_conv2d16.h"),
-               os.path.join(inc, "satools_hip_ragged.h"), os.path.join(inc, "satools_hip_ragged2d.h"), os.path.join(inc, "satools_hip_ragged2d16.h"),
-               os.path.join(inc, "satools_hip_yaapt_long.h"), os.path.join(inc, "satools_hip_geninput.h")])
+    """what every object depends on besides its own source: every header under csrc/ and the public ones"""
+    return (glob.glob(os.path.join(HERE, "csrc", "**", "*.h"), recursive=True)
+            + glob.glob(os.path.join(HERE, "..", "include", "satools_hip*.h")))
 
 
 def object_name(src):
-    """csrc/x.hip -> x.hip.o, csrc/stats/x.hip -> stats_x.hip.o, csrc/conv2d16/x.hip -> conv2d16_x.hip.o, csrc/ragged/x.hip ->
-    ragged_x.hip.o, csrc/ragged2d/x.hip -> ragged2d_x.hip.o, csrc/ragged2d16/x.hip -> ragged2d16_x.hip.o, csrc/yaapt_long/x.hip -> yaapt_long_x.hip.o,
-    csrc/geninput/x.hip -> geninput_x.hip.o: a file name may repeat between the directories"""
+    """csrc/x.hip -> x.hip.o, csrc/<name>/x.hip -> <name>_x.hip.o: a file name may repeat between the directories"""
     rel = os.path.relpath(src, os.path.join(HERE, "csrc"))
     return rel.replace(os.sep, "_") + ".o"
 

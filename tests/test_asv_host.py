@@ -36,16 +36,16 @@ def test_new_entries_are_declared_exported_and_bound():
     for name in NEW:
         assert re.search(r"\bint " + name + r"\(", header), name
         assert hasattr(lib, name), name
-        assert name in _lib.exported_symbols()
+        assert name in _lib.symbols("core")
     from satools_amd import ops
     for fn in ("cohort_topk_stats", "trial_scores", "segment_mean_l2norm"):
         assert callable(getattr(ops, fn))
 
 
 def test_a_library_without_a_bound_symbol_is_reported_with_the_build_command(monkeypatch):
-    """what a library built before the ASV entries existed looks like to the binding: a name of _PROTOS that dlsym cannot find"""
+    """what a library built before the ASV entries existed looks like to the binding: a name of the table that dlsym cannot find"""
     import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS, "sat_entry_of_a_newer_tree_f32", (C.c_int, []))
+    monkeypatch.setitem(_lib.COMPONENTS["core"], "sat_entry_of_a_newer_tree_f32", (C.c_int, []))
     monkeypatch.setattr(_lib, "_lib", None)
     with pytest.raises(_lib.SatError, match=r"does not export sat_entry_of_a_newer_tree_f32.*build\.py"):
         _lib.lib()

@@ -1,7 +1,7 @@
 """Host side of the split-f16 2-D convolutions (csrc/conv2d16/, include/satools_hip_conv2d16.h), CPU only: the weight packing, the
 emulation of the kernel's arithmetic (tests/ref_split16.py) against float64 inside the bound of tests/test_hip_conv2d16.py and through the
-whole ResNet against the reference's x-vectors, the gates that tie the new header and source directory to that file's bounds table (as
-tests/test_eer_host.py does for include/satools_hip_stats.h), and the plumbing of `conv2d_precision`."""
+whole ResNet against the reference's x-vectors, the header's constant and the conditions on that file's bounds rows (header, binding and
+table are held together by tests/test_components_host.py), and the plumbing of `conv2d_precision`."""
 import os
 import re
 
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_decl
 import ref_split16
 import test_hip_conv2d16 as hc
 from satools_amd import _lib, ops, packing
@@ -125,70 +126,20 @@ def test_emulated_resnet_meets_the_x_vector_bar(tag, seed, n):
     assert err < 5e-6 and cos > 0.999999
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------------
-def _entry_points(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-
-
-def test_conv2d16_header_is_bound_and_exported_and_the_other_headers_are_unchanged():
-    names = _entry_points(HEADER)
-    assert names == [ENTRY] == _lib.conv2d16_symbols()
-    lib = _lib.lib()
-    for n in names:
-        assert hasattr(lib, n) and getattr(lib, n).argtypes is not None and len(getattr(lib, n).argtypes) == 16, n
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert "f16x3_f32" not in main_header and "conv2d16" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    assert ENTRY not in _lib.exported_symbols() and set(_lib.exported_symbols()) <= set(_entry_points("satools_hip.h"))
-    assert _entry_points("satools_hip_stats.h") == _lib.stats_symbols() == ["sat_eer_bootstrap_i32"]
-    limit = float(re.search(r"#define SAT_CONV2D16_SPLIT_LIMIT ([0-9.]+)f", open(os.path.join(ROOT, "include", HEADER)).read()).group(1))
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library, build and bounds table together) ----
+def test_conv2d16_header_limit_is_the_largest_f16_and_the_emulations():
+    text = abi_decl.define(HEADER, "SAT_CONV2D16_SPLIT_LIMIT")
+    limit = float(re.fullmatch(r"([0-9.]+)f", text).group(1))
     assert limit == ref_split16.SPLIT_LIMIT == 65520.0
     assert float(torch.tensor(np.nextafter(np.float32(limit), np.float32(0))).half()) == 65504.0 and torch.isinf(torch.tensor(limit).half())
+    assert len(_lib.COMPONENTS["conv2d16"][ENTRY][1]) == 16
     assert callable(ops.conv2d_f16x3) and callable(ops.pack_conv2d_weight_f16x3)
 
 
-def test_a_library_without_the_conv2d16_entry_is_reported_with_the_build_command(monkeypatch):
-    import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS_CONV2D16, "sat_conv2d16_entry_of_a_newer_tree_f32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_conv2d16_entry_of_a_newer_tree_f32.*older source tree.*build\.py"):
-        _lib.lib()
-
-
-def test_build_knows_the_new_directory_and_header():
-    from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "conv2d16" + os.sep in s]
-    assert src and all(build.object_name(s).startswith("conv2d16_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
-
-
-# ---- the gates of the new component ----------------------------------------------------------------------------------------------
-def test_every_conv2d16_entry_point_has_a_bounds_row():
-    names = _entry_points(HEADER)
-    assert names
-    rows = {r.entry for r in hc.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    missing = [n for n in names if n not in rows]
-    assert not missing, f"entry points without a bounds row: {missing}"
-    assert not [r for r in rows if r not in names]
-    for r in hc.ROWS:
-        assert r.shapes, r.name
+def test_the_conv2d16_bounds_rows_run_with_and_without_the_flag_and_the_epilogue():
     flags = {s[8] for r in hc.ROWS for s in r.shapes}
     epis = {s[7] for r in hc.ROWS for s in r.shapes}
     assert flags == {True, False} and {"none", "affine_relu"} <= epis
-
-
-def test_the_conv2d16_dispatch_family_list_is_the_one_in_the_sources():
-    src = os.path.join(ROOT, "sa-toolkit_amd", "csrc", "conv2d16")
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    assert names and set(hc.FAMILIES) == names and len(hc.FAMILIES) == len(set(hc.FAMILIES)), (sorted(names), hc.FAMILIES)
 
 
 def test_the_gpu_tests_shapes_straddle_the_kernels_tiles():

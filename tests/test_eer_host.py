@@ -1,22 +1,20 @@
 """Host side of the bootstrap interval of the EER, CPU only: the generator of tests/ref64_eer.py against the published Philox known
 answers, satools_amd.asv_eval.empirical_eer / eer_cuts against the definition evaluated threshold by threshold, the argument checks of
-ops.eer_bootstrap, the unchanged default of the metric functions, the report lines, the C-ABI surface of include/satools_hip_stats.h, and
-the two gates that tie that header and csrc/stats/ to the bounds table of tests/test_hip_eer_bootstrap.py (as tests/test_moat_host.py ties
-include/satools_hip.h and csrc/ to tests/test_hip_bounds.py).  Everything compared here is integers or the same float64 division on both
-sides: equality, no tolerance."""
+ops.eer_bootstrap, the unchanged default of the metric functions, the report lines, and the constant of include/satools_hip_stats.h (the
+header, the binding and the bounds table are held together by tests/test_components_host.py).  Everything compared here is integers or the
+same float64 division on both sides: equality, no tolerance."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_decl
 import ref64_eer
 from satools_amd import _lib, asv_eval, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY = "sat_eer_bootstrap_i32"
 WORKED = [([3, 4, 5], [0, 1, 2], 0.0, None), ([0, 1, 2], [3, 4, 5], 1.0, None), ([0], [0], 1.0, None), ([1], [0], 0.0, None),
           ([0, 0, 1, 1, 2], [0, 1, 1, 2, 2, 2], 0.8, (4, 5))]
 
@@ -236,56 +234,8 @@ def test_command_line_has_the_new_options(capsys):
     assert "--eer-ci M" in text and "--eer-ci-seed S" in text and "--report" in text
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------
-def _entry_points(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-
-
-def test_stats_header_is_bound_and_exported_and_the_main_header_is_unchanged():
-    names = _entry_points("satools_hip_stats.h")
-    assert names == [ENTRY] == _lib.stats_symbols()
-    lib = _lib.lib()
-    for n in names:
-        assert hasattr(lib, n) and getattr(lib, n).argtypes is not None, n
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert "eer_bootstrap" not in main_header and int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8
-    assert ENTRY not in _lib.exported_symbols() and set(_lib.exported_symbols()) <= set(_entry_points("satools_hip.h"))
-    stats_header = open(os.path.join(ROOT, "include", "satools_hip_stats.h")).read()
-    maximum = int(re.search(r"#define SAT_EER_BOOTSTRAP_MAX_SIDE (\d+)", stats_header).group(1))
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library, build and bounds table together) ----
+def test_stats_header_maximum_is_the_one_ops_checks():
+    maximum = int(abi_decl.define("satools_hip_stats.h", "SAT_EER_BOOTSTRAP_MAX_SIDE"))
     assert maximum >= 2 ** 20 and maximum == ops.EER_BOOTSTRAP_MAX_SIDE
     assert callable(ops.eer_bootstrap) and callable(asv_eval.eer_interval)
-
-
-def test_a_library_without_the_stats_entry_is_reported_with_the_build_command(monkeypatch):
-    import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS_STATS, "sat_stats_entry_of_a_newer_tree_i32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_stats_entry_of_a_newer_tree_i32.*build\.py"):
-        _lib.lib()
-
-
-# ---- the gates of the new component ----------------------------------------------------------------------------------------
-def test_every_stats_entry_point_has_a_bounds_row():
-    import test_hip_eer_bootstrap as hb
-    names = _entry_points("satools_hip_stats.h")
-    assert names
-    rows = {r.entry for r in hb.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    missing = [n for n in names if n not in rows]
-    assert not missing, f"entry points without a bounds row: {missing}"
-    assert not [r for r in rows if r not in names]
-    for r in hb.ROWS:
-        assert r.shapes, r.name
-
-
-def test_the_stats_dispatch_family_list_is_the_one_in_the_sources():
-    import test_hip_eer_bootstrap as hb
-    src = os.path.join(ROOT, "sa-toolkit_amd", "csrc", "stats")
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    assert names and set(hb.FAMILIES) == names and len(hb.FAMILIES) == len(set(hb.FAMILIES)), (sorted(names), hb.FAMILIES)

@@ -1,9 +1,6 @@
 """The red-zone helper (tests/moat.py) proven on the CPU: tiny torch stand-ins for kernels, one honest and ten with an injected fault,
-each of which must be reported with the right buffer, role and byte offset — and the coverage gate of tests/test_hip_bounds.py: every
-entry point of include/satools_hip.h has a row there or is exempt because it launches no kernel."""
-import os
-import re
-
+each of which must be reported with the right buffer, role and byte offset.  (The coverage gate of tests/test_hip_bounds.py — every entry
+point of include/satools_hip.h has a row there or is exempt because it launches no kernel — is in tests/test_components_host.py.)"""
 import torch
 
 import moat
@@ -195,47 +192,3 @@ def test_dont_care_input_pad_must_not_reach_a_result():
     assert run_case(specs, ok)[0] == []
     ru = _only(run_case(specs, leaky)[0], "R/U")
     assert ru[0].buf == "y" and ru[0].first < 4
-
-
-# ---- the coverage gate ---------------------------------------------------------------------------------
-def _header_entry_points():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "satools_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-
-
-def test_every_entry_point_has_a_bounds_row_or_launches_no_kernel():
-    import test_hip_bounds as hb
-    names = _header_entry_points()
-    assert len(names) == len(set(names)) >= 80 and "sat_conv1d_f32" in names and "sat_row_mean_std_f32" in names
-    rows = {r.entry for r in hb.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    for n, why in hb.EXEMPT.items():
-        assert n in names, f"{n} is exempt but not in the header"
-        assert n not in rows, f"{n} is exempt and has a row"
-        assert why.startswith("launches no kernel") or (n == "sat_clock_probe" and why.startswith("diagnostic")), (n, why)
-    missing = [n for n in names if n not in rows and n not in hb.EXEMPT]
-    assert not missing, f"entry points without a bounds row: {missing}"
-    assert not [r for r in rows if r not in names]
-    for r in hb.ROWS:
-        assert r.shapes, r.name
-
-
-def test_the_dispatch_family_list_is_the_one_in_the_sources():
-    """FAMILIES + INNER of the bounds table = the SAT_LAUNCH_CHECK strings of csrc/ (the diagnostic clock probe aside): a new kernel family
-    without a row that reaches it fails here, before it fails on the GPU"""
-    import test_hip_bounds as hb
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, "sa-toolkit_amd", "csrc")
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    names.discard("clock_probe_kernel")
-    assert len(names) > 60
-    listed = set(hb.FAMILIES) | set(hb.INNER)
-    assert listed == names, (sorted(names - listed), sorted(listed - names))
-    assert len(hb.FAMILIES) == len(set(hb.FAMILIES)) and not set(hb.FAMILIES) & set(hb.INNER)
-    assert set(hb.INNER.values()) <= {r.entry for r in hb.ROWS}

@@ -80,7 +80,7 @@ class Recorder:
     def __getattr__(self, name):
         if not name.startswith("sat_"):
             raise AttributeError(name)
-        argtypes = _lib._PROTOS[name][1]
+        argtypes = _lib.COMPONENTS["core"][name][1]
 
         def call(*args):
             assert len(args) == len(argtypes), name

@@ -1,7 +1,7 @@
 """Host side of the clean and many-to-one anonymizer configs (sa-toolkit_amd/anonymizer_variants.py) and of the generator-input
 component (csrc/geninput/, include/satools_hip_geninput.h), CPU only: loading, key lists, the SpeakerCMVN buffer, the float64
-restatement against the reference's recorded runs (tests/golden/fx_variants.npz), and the gates that tie header, source directory and
-binding together."""
+restatement against the reference's recorded runs (tests/golden/fx_variants.npz), and the component's constants and refusals (header,
+descriptor, binding and build are held together by tests/test_components_host.py)."""
 import ctypes as C
 import json
 import os
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_decl
 import ref64_geninput as r64
 from satools_amd import _lib
 
@@ -160,36 +161,11 @@ def test_ref64_m2o_rows_are_batch_coupled(fx):
     assert bool((fx[p + "f0_after"] == 123.0).all()) and bool((fx[p + "f0"] == 123.0).all())
 
 
-# ---- header, binding, library, build ---------------------------------------------------------------------------------------------------------
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
-
-
-def test_geninput_header_is_bound_and_exported():
-    text = _header_code()
-    names = sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-    assert names == ["sat_generator_input_f32"] == _lib.geninput_symbols() == sorted(_lib._PROTOS_GENINPUT)
-    lib = _lib.lib()
-    fn = lib.sat_generator_input_f32
-    assert fn.restype is C.c_int and fn.argtypes == _lib._PROTOS_GENINPUT["sat_generator_input_f32"][1]
-    assert re.search(r"int sat_generator_input_f32\(const sat_geninput_desc\* d, void\* stream\);", text)
-    # the descriptor, field by field
-    body = re.search(r"typedef struct sat_geninput_desc \{(.*?)\} sat_geninput_desc;", text, flags=re.S).group(1)
-    fields = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        kind, rest = re.match(r"((?:const )?\w+\*?)\s+(.*)", decl).groups()
-        fields += [(n.strip(), kind) for n in rest.split(",")]
-    ctype = {"int32_t": C.c_int32, "int64_t": C.c_int64, "const float*": C.c_void_p, "float*": C.c_void_p, "const int32_t*": C.c_void_p}
-    assert [(n, ctype[k]) for n, k in fields] == list(_lib.GenInputDesc._fields_)
-    assert C.sizeof(_lib.GenInputDesc) == 10 * 4 + 3 * 8 + 8 * 8
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert "generator_input" not in main_header and "geninput" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    others = (set(_lib.exported_symbols()) | set(_lib.stats_symbols()) | set(_lib.conv2d16_symbols()) | set(_lib.ragged_symbols())
-              | set(_lib.ragged2d_symbols()) | set(_lib.ragged2d16_symbols()) | set(_lib.yaapt_long_symbols()))
-    assert not set(names) & others
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, descriptor, library and build together) ----
+def test_geninput_declaration_and_tile_constants():
+    assert re.search(r"int sat_generator_input_f32\(const sat_geninput_desc\* d, void\* stream\);", abi_decl.code(HEADER))
     src = open(os.path.join(ROOT, "sa-toolkit_amd", "csrc", "geninput", "generator_input.hip")).read()
-    assert int(re.search(r"#define SAT_GENINPUT_TILE (\d+)", open(os.path.join(ROOT, "include", HEADER)).read()).group(1)) == 64
+    assert int(abi_decl.define(HEADER, "SAT_GENINPUT_TILE")) == 64
     assert "constexpr int GI_TILE = SAT_GENINPUT_TILE;" in src and "constexpr int GI_PITCH = GI_TILE + 1;" in src and "atomic" not in src.lower()
 
 
@@ -198,15 +174,6 @@ def test_refusals_need_no_gpu():
     assert lib.sat_generator_input_f32(None, None) == -1 and b"generator_input: null descriptor" in lib.sat_last_error()
     d = _lib.GenInputDesc()
     assert lib.sat_generator_input_f32(C.byref(d), None) == -1 and b"generator_input: null pointer" in lib.sat_last_error()
-
-
-def test_build_knows_the_new_directory_and_header():
-    from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "geninput" + os.sep in s]
-    assert [os.path.basename(s) for s in src] == ["generator_input.hip"] and all(build.object_name(s).startswith("geninput_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(os.sep + HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
-    assert "geninput_x.hip.o" in build.object_name.__doc__
 
 
 def test_the_existing_kernels_sources_are_restated_not_shared():

@@ -1,7 +1,7 @@
 """Host side of the ragged x-vector batches (csrc/ragged/, include/satools_hip_ragged.h), CPU only: the packed layout and the tile table
-(ops.ragged_layout / ragged_tiles), the grouping of asv_eval's extraction with a stub model that records its calls, and the gates that tie the
-new header and source directory to the bounds table of tests/test_hip_xvector_ragged.py (as tests/test_conv2d16_host.py does for
-include/satools_hip_conv2d16.h)."""
+(ops.ragged_layout / ragged_tiles), the grouping of asv_eval's extraction with a stub model that records its calls, and the shapes of
+tests/test_hip_xvector_ragged.py against the kernels' constants (header, binding and bounds table are held together by
+tests/test_components_host.py)."""
 import os
 import re
 
@@ -14,8 +14,6 @@ from satools_amd import _lib, asv_eval, ops, pipeline
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = "satools_hip_ragged.h"
-ENTRIES = ["sat_attentive_stats_segments_f32", "sat_instnorm_segments_f32", "sat_melspec_logmel_segments_f32", "sat_res2_chain_segments_f32",
-           "sat_row_mean_segments_f32", "sat_se_gate_add_segments_f32"]
 
 
 # ---- the packed layout -----------------------------------------------------------------------------------------------------------
@@ -169,72 +167,11 @@ def test_extract_batch_checks_its_arguments_before_any_device_call(monkeypatch):
         net.extract_batch([])
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------------
-def _entry_points(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-
-
-def test_ragged_header_is_bound_and_exported_and_the_other_headers_are_unchanged():
-    names = _entry_points(HEADER)
-    assert names == ENTRIES == _lib.ragged_symbols()
-    lib = _lib.lib()
-    for n in names:
-        fn = getattr(lib, n)
-        assert fn.argtypes is not None and fn.argtypes == _lib._PROTOS_RAGGED[n][1], n
-    # the argument counts of the prototypes are those of the header
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
-    for n in names:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", text).group(1)
-        assert len(decl.split(",")) == len(_lib._PROTOS_RAGGED[n][1]), n
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert not [n for n in names if n in main_header] and "satools_hip_ragged" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    assert not set(names) & set(_lib.exported_symbols()) and set(_lib.exported_symbols()) <= set(_entry_points("satools_hip.h"))
-    assert _entry_points("satools_hip_stats.h") == _lib.stats_symbols() and _entry_points("satools_hip_conv2d16.h") == _lib.conv2d16_symbols()
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library, build and bounds table together) ----
+def test_ops_has_the_wrappers_of_the_ragged_entries():
     for name in ("ragged_layout", "ragged_tiles", "melspec_logmel_segments", "instnorm_segments", "row_mean_segments", "se_gate_add_segments",
                  "attentive_stats_segments", "res2_chain_segments"):
         assert callable(getattr(ops, name)), name
-
-
-def test_a_library_without_a_ragged_entry_is_reported_with_the_build_command(monkeypatch):
-    import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS_RAGGED, "sat_ragged_entry_of_a_newer_tree_f32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_ragged_entry_of_a_newer_tree_f32.*older source tree.*build\.py"):
-        _lib.lib()
-
-
-def test_build_knows_the_new_directory_and_header():
-    from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "ragged" + os.sep in s]
-    assert src and all(build.object_name(s).startswith("ragged_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
-
-
-# ---- the gates of the new component ----------------------------------------------------------------------------------------------
-def test_every_ragged_entry_point_has_a_bounds_row():
-    names = _entry_points(HEADER)
-    assert names
-    rows = {r.entry for r in hr.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    missing = [n for n in names if n not in rows]
-    assert not missing, f"entry points without a bounds row: {missing}"
-    assert not [r for r in rows if r not in names]
-    for r in hr.ROWS:
-        assert r.shapes, r.name
-
-
-def test_the_ragged_dispatch_family_list_is_the_one_in_the_sources():
-    src = os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged")
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    assert names and set(hr.FAMILIES) == names and len(hr.FAMILIES) == len(set(hr.FAMILIES)), (sorted(names), hr.FAMILIES)
 
 
 def test_the_gpu_tests_shapes_straddle_the_wave_and_the_chains_centres():

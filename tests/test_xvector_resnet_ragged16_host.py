@@ -1,6 +1,6 @@
-"""Host side of the split-f16 2-D convs in ragged batches (csrc/ragged2d16/, include/satools_hip_ragged2d16.h), CPU only: the gates that
-tie the new header and source directory to the binding and to the bounds table of tests/test_hip_xvector_resnet_ragged16.py (as
-tests/test_xvector_resnet_ragged_host.py does for include/satools_hip_ragged2d.h), xvector_resnet.Net.ragged_conv2d_precision and the weights
+"""Host side of the split-f16 2-D convs in ragged batches (csrc/ragged2d16/, include/satools_hip_ragged2d16.h), CPU only: the entry's
+declaration and the conditions on the bounds rows of tests/test_hip_xvector_resnet_ragged16.py (header, binding and table are held
+together by tests/test_components_host.py), xvector_resnet.Net.ragged_conv2d_precision and the weights
 it packs, asv-eval --resnet-conv2d-ragged, and the float64 calibration of the GPU file's partial fallback."""
 import os
 import re
@@ -8,6 +8,7 @@ import re
 import pytest
 import torch
 
+import abi_decl
 import ref64
 import ref64_resnet
 import test_hip_xvector_resnet_ragged16 as hr
@@ -16,73 +17,19 @@ from satools_amd import _lib, asv_eval, ops, xvector_resnet
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = "satools_hip_ragged2d16.h"
 SOURCE = os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged2d16", "conv2d_f16x3_segments.hip")
-ENTRIES = ["sat_conv2d_f16x3_segments_f32"]
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------------
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
-
-
-def _entry_points():
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", _header_code())))
-
-
-def test_ragged2d16_header_is_bound_and_exported_in_both_directions():
-    names = _entry_points()
-    assert names == ENTRIES == _lib.ragged2d16_symbols() == sorted(_lib._PROTOS_RAGGED2D16)
-    lib = _lib.lib()
-    text = _header_code()
-    kinds = {"int": "c_int", "float": "c_float", "void*": "c_void_p", "const void*": "c_void_p", "const float*": "c_void_p", "float*": "c_void_p",
-             "const int32_t*": "c_void_p", "int32_t*": "c_void_p"}
-    for n in names:
-        fn = getattr(lib, n)
-        assert fn.argtypes is not None and fn.argtypes == _lib._PROTOS_RAGGED2D16[n][1], n
-        decl = [re.sub(r"\s*\w+$", "", a.strip()) for a in re.search(r"\b" + n + r"\s*\(([^)]*)\)", text).group(1).split(",")]
-        assert [kinds[d] for d in decl] == [t.__name__ for t in _lib._PROTOS_RAGGED2D16[n][1]], n       # every argument's kind, in order
-    # the declaration is the one of the issue, names included
-    args = re.sub(r"\s+", " ", re.search(r"sat_conv2d_f16x3_segments_f32\s*\(([^)]*)\)", text).group(1))
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library, build and bounds table together) ----
+def test_the_declaration_is_the_one_of_the_issue_names_included():
+    args = re.sub(r"\s+", " ", re.search(r"sat_conv2d_f16x3_segments_f32\s*\(([^)]*)\)", abi_decl.code(HEADER)).group(1))
     assert args == ("const float* x, const void* w_split, float w_descale, float* y, const float* ch_scale, const float* ch_shift, int relu, "
                     "const int32_t* in_off, const int32_t* in_len, const int32_t* out_off, int B, int max_len, int Cin, int Cout, int H, int T_in, "
                     "int T_out, int ksize, int stride, int32_t* overflow_flags, void* stream")
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert not [n for n in names if n in main_header] and "ragged2d16" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    others = (set(_lib.exported_symbols()) | set(_lib.stats_symbols()) | set(_lib.conv2d16_symbols()) | set(_lib.ragged_symbols())
-              | set(_lib.ragged2d_symbols()))
-    assert not set(names) & others
-    for other in ("satools_hip_ragged2d.h", "satools_hip_conv2d16.h"):              # the parents' entry lists are what they were
-        code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", other)).read(), flags=re.S)
-        assert not [n for n in names if n in code], other
     assert callable(ops.conv2d_f16x3_segments)
     assert "satools_hip_ragged2d16.h" in open(os.path.join(ROOT, "include", "satools_hip_ragged2d.h")).read()      # the pointer to the new header
 
 
-def test_a_library_without_the_ragged2d16_entry_is_reported_with_the_build_command(monkeypatch):
-    import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS_RAGGED2D16, "sat_ragged2d16_entry_of_a_newer_tree_f32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_ragged2d16_entry_of_a_newer_tree_f32.*older source tree.*build\.py"):
-        _lib.lib()
-
-
-def test_build_knows_the_new_directory_and_header():
-    from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "ragged2d16" + os.sep in s]
-    assert [os.path.basename(s) for s in src] == ["conv2d_f16x3_segments.hip"] and all(build.object_name(s).startswith("ragged2d16_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(os.sep + HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
-    doc = build.object_name.__doc__
-    for example in ("x.hip.o", "stats_x.hip.o", "conv2d16_x.hip.o", "ragged_x.hip.o", "ragged2d_x.hip.o", "ragged2d16_x.hip.o"):
-        assert example in doc, example
-
-
-# ---- the gates of the new component ----------------------------------------------------------------------------------------------
-def test_every_ragged2d16_entry_point_has_a_bounds_row_with_and_without_a_broken_table():
-    names = _entry_points()
-    rows = {r.entry for r in hr.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    assert names and sorted(rows) == names
+def test_every_ragged2d16_bounds_row_runs_with_and_without_a_broken_table_on_every_instantiation():
     for r in hr.ROWS:
         assert r.shapes and any(s[-1] for s in r.shapes) and any(not s[-1] for s in r.shapes), r.name      # with and without the broken entry
         assert {s[-1] for s in r.shapes} == {"", "in", "out"}                       # on either side
@@ -91,17 +38,11 @@ def test_every_ragged2d16_entry_point_has_a_bounds_row_with_and_without_a_broken
     assert hr.BROKEN < len(hr.WIDTHS)
 
 
-def test_the_ragged2d16_dispatch_family_list_is_the_one_in_the_sources():
-    src = os.path.dirname(SOURCE)
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    assert names and set(hr.FAMILIES) == names and len(hr.FAMILIES) == len(set(hr.FAMILIES)), (sorted(names), hr.FAMILIES)
-    # names the codegen tests of the other components count by substring
+def test_the_ragged2d16_family_names_are_not_counted_by_the_other_components_codegen_tests():
+    """names the codegen tests of the other components count by substring"""
+    assert hr.FAMILIES
     for other in ("conv2d_f16x3_kernel", "conv2d_mfma_kernel", "conv2d_segments_mfma_kernel", "conv2d_stem_kernel"):
-        assert not [n for n in names if other in n], other
+        assert not [n for n in hr.FAMILIES if other in n], other
 
 
 def test_the_gpu_tests_widths_are_the_ones_the_sources_tile_constants_need():

@@ -1,7 +1,7 @@
 """Host side of the ragged batches of the ResNet x-vector extractor (csrc/ragged2d/, include/satools_hip_ragged2d.h), CPU only: the tables
-of the four time resolutions (ops.ragged_levels / ragged_column_segments), the gates that tie the new header and source directory to the
-binding and to the bounds table of tests/test_hip_xvector_resnet_ragged.py (as tests/test_xvector_ragged_host.py does for
-include/satools_hip_ragged.h), and extract_batch's argument checks, which come before any device call."""
+of the four time resolutions (ops.ragged_levels / ragged_column_segments), the conditions on the bounds rows and shapes of
+tests/test_hip_xvector_resnet_ragged.py (header, binding and table are held together by tests/test_components_host.py), and
+extract_batch's argument checks, which come before any device call."""
 import os
 import re
 
@@ -14,7 +14,6 @@ from satools_amd import _lib, ops, xvector_resnet
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = "satools_hip_ragged2d.h"
-ENTRIES = ["sat_conv2d_segments_f32", "sat_plane_mean_segments_f32", "sat_row_mean_std_segments_f32", "sat_se_scale_add_relu_segments_f32"]
 
 
 # ---- the tables ------------------------------------------------------------------------------------------------------------------
@@ -119,68 +118,15 @@ class _OnDevice(torch.Tensor):
     is_cuda = property(lambda self: True)
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------------
-def _entry_points(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sat_\w+)\s*\(", text)))
-
-
-def test_ragged2d_header_is_bound_and_exported_in_both_directions():
-    names = _entry_points(HEADER)
-    assert names == ENTRIES == _lib.ragged2d_symbols() == sorted(_lib._PROTOS_RAGGED2D)
-    lib = _lib.lib()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
-    kinds = {"int": "c_int", "void*": "c_void_p", "const float*": "c_void_p", "float*": "c_void_p", "const int32_t*": "c_void_p"}
-    for n in names:
-        fn = getattr(lib, n)
-        assert fn.argtypes is not None and fn.argtypes == _lib._PROTOS_RAGGED2D[n][1], n
-        decl = [re.sub(r"\s*\w+$", "", a.strip()) for a in re.search(r"\b" + n + r"\s*\(([^)]*)\)", text).group(1).split(",")]
-        assert [kinds[d] for d in decl] == [t.__name__ for t in _lib._PROTOS_RAGGED2D[n][1]], n      # every argument's kind, in order
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert not [n for n in names if n in main_header] and "satools_hip_ragged2d" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    others = set(_lib.exported_symbols()) | set(_lib.stats_symbols()) | set(_lib.conv2d16_symbols()) | set(_lib.ragged_symbols())
-    assert not set(names) & others
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library, build and bounds table together) ----
+def test_ops_has_the_wrappers_of_the_ragged2d_entries():
     for name in ("ragged_levels", "RaggedLevels", "conv2d_segments", "plane_mean_segments", "se_scale_add_relu_segments", "row_mean_std_segments"):
         assert callable(getattr(ops, name)), name
 
 
-def test_a_library_without_a_ragged2d_entry_is_reported_with_the_build_command(monkeypatch):
-    import ctypes as C
-    monkeypatch.setitem(_lib._PROTOS_RAGGED2D, "sat_ragged2d_entry_of_a_newer_tree_f32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_ragged2d_entry_of_a_newer_tree_f32.*older source tree.*build\.py"):
-        _lib.lib()
-
-
-def test_build_knows_the_new_directory_and_header():
-    from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "ragged2d" + os.sep in s]
-    assert src and all(build.object_name(s).startswith("ragged2d_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
-    assert "ragged2d_x.hip.o" in build.object_name.__doc__
-
-
-# ---- the gates of the new component ----------------------------------------------------------------------------------------------
-def test_every_ragged2d_entry_point_has_a_bounds_row_with_a_broken_table():
-    names = _entry_points(HEADER)
-    rows = {r.entry for r in hr.ROWS}
-    assert not torch.cuda.is_initialized()          # importing the table touches no GPU
-    assert names and sorted(rows) == names
+def test_every_ragged2d_bounds_row_runs_with_and_without_a_broken_table():
     for r in hr.ROWS:
         assert r.shapes and any(s[-1] for s in r.shapes) and any(not s[-1] for s in r.shapes), r.name      # with and without the broken entry
-
-
-def test_the_ragged2d_dispatch_family_list_is_the_one_in_the_sources():
-    src = os.path.join(ROOT, "sa-toolkit_amd", "csrc", "ragged2d")
-    names = set()
-    for f in sorted(os.listdir(src)):
-        if f.endswith((".hip", ".h")):
-            for args in re.findall(r"SAT_LAUNCH_CHECK\(([^;]*)\);", open(os.path.join(src, f)).read()):
-                names.update(re.findall(r'"([^"]+)"', args))
-    assert names and set(hr.FAMILIES) == names and len(hr.FAMILIES) == len(set(hr.FAMILIES)), (sorted(names), hr.FAMILIES)
 
 
 def test_the_gpu_tests_shapes_are_the_ones_the_kernels_edges_need():

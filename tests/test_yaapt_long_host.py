@@ -1,7 +1,7 @@
 """Host side of YAAPT beyond 2048 frames (csrc/yaapt_long/, include/satools_hip_yaapt_long.h), CPU only: the catalogue of
-tests/yaapt_long_cases.py held against the float32 oracle and the reference's tracks (tests/golden/fx_f0_long.npz), the gates that tie the new
-header and source directory to the binding, the chunk walk of the long kernels restated in plain Python with its constants pinned to the
-source, and the dispatch f0.track."""
+tests/yaapt_long_cases.py held against the float32 oracle and the reference's tracks (tests/golden/fx_f0_long.npz), the chunk walk of the
+long kernels restated in plain Python with its constants pinned to the source, and the dispatch f0.track (header, binding and build are
+held together by tests/test_components_host.py)."""
 import ctypes as C
 import os
 import re
@@ -19,7 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "sa-toolkit_amd", "csrc")
 HEADER = "satools_hip_yaapt_long.h"
 SOURCE = os.path.join(CSRC, "yaapt_long", "yaapt_long.hip")
-ENTRIES = ["sat_yaapt_long_f32", "sat_yaapt_long_workspace_bytes"]
 
 
 @pytest.fixture(autouse=True)
@@ -68,49 +67,12 @@ def test_the_straddle_case_declares_130_frames():
     assert ylc.STRADDLE.nframes == 130 and not x[61 * 320 + 100:66 * 320 + 200].any() and x[:61 * 320].any() and x[67 * 320:].any()
 
 
-# ---- header, binding, library ------------------------------------------------------------------------------------------------------------
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
-
-
-def test_yaapt_long_header_is_bound_and_exported_in_both_directions():
-    names = sorted(set(re.findall(r"\b(sat_\w+)\s*\(", _header_code())))
-    assert names == ENTRIES == _lib.yaapt_long_symbols() == sorted(_lib._PROTOS_YAAPT_LONG)
-    lib = _lib.lib()
-    text = _header_code()
-    kinds = {"int": "c_int", "size_t": C.c_size_t.__name__, "void*": "c_void_p", "const float*": "c_void_p", "float*": "c_void_p",
-             "const int32_t*": "c_void_p", "int32_t*": "c_void_p", "const sat_yaapt_plan*": "c_void_p"}
-    for n in names:
-        fn = getattr(lib, n)
-        assert fn.argtypes is not None and fn.argtypes == _lib._PROTOS_YAAPT_LONG[n][1], n
-        decl = [re.sub(r"\s*\w+$", "", a.strip()) for a in re.search(r"\b" + n + r"\s*\(([^)]*)\)", text).group(1).split(",")]
-        assert [kinds[d] for d in decl] == [t.__name__ for t in _lib._PROTOS_YAAPT_LONG[n][1]], n       # every argument's kind, in order
-    assert lib.sat_yaapt_long_workspace_bytes.restype is C.c_size_t and lib.sat_yaapt_long_f32.restype is C.c_int
-    main_header = open(os.path.join(ROOT, "include", "satools_hip.h")).read()
-    assert not [n for n in names if n in main_header] and "yaapt_long" not in main_header
-    assert int(re.search(r"#define SAT_ABI_VERSION (\d+)", main_header).group(1)) == 8 and lib.sat_abi_version() == 8
-    others = (set(_lib.exported_symbols()) | set(_lib.stats_symbols()) | set(_lib.conv2d16_symbols()) | set(_lib.ragged_symbols())
-              | set(_lib.ragged2d_symbols()) | set(_lib.ragged2d16_symbols()))
-    assert not set(names) & others
-    assert callable(f0_hip.yaapt_long) and callable(f0_hip.track)
-
-
-def test_a_library_without_the_long_entry_is_reported_with_the_build_command(monkeypatch):
-    monkeypatch.setitem(_lib._PROTOS_YAAPT_LONG, "sat_yaapt_long_entry_of_a_newer_tree_f32", (C.c_int, []))
-    monkeypatch.setattr(_lib, "_lib", None)
-    with pytest.raises(_lib.SatError, match=r"does not export sat_yaapt_long_entry_of_a_newer_tree_f32.*older source tree.*build\.py"):
-        _lib.lib()
-
-
-def test_build_knows_the_new_directory_and_header():
+# ---- what is particular to this component (tests/test_components_host.py holds header, binding, library and build together) ---------------
+def test_f0_has_the_long_form_and_the_build_depends_on_the_headers_it_shares_with_the_resident_form():
     from satools_amd import build
-    src = [s for s in build.sources() if os.sep + "yaapt_long" + os.sep in s]
-    assert [os.path.basename(s) for s in src] == ["yaapt_long.hip"] and all(build.object_name(s).startswith("yaapt_long_") for s in src)
-    assert len({build.object_name(s) for s in build.sources()}) == len(build.sources())
-    assert any(h.endswith(os.sep + HEADER) for h in build.headers()) and all(os.path.exists(h) for h in build.headers())
+    assert callable(f0_hip.yaapt_long) and callable(f0_hip.track)
     for shared in ("yaapt_dev.h", "yaapt_spec_select_body.h", "yaapt_refine_body.h"):
         assert any(h.endswith(os.sep + shared) for h in build.headers()), shared
-    assert "yaapt_long_x.hip.o" in build.object_name.__doc__
 
 
 def test_workspace_bytes_and_the_chunk_set_without_a_gpu():
