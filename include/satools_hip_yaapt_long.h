@@ -14,6 +14,15 @@
  * arithmetic and its order are those of sat_yaapt_f32: on a plan of 4 .. 2048 frames the track, the status words and every view of the
  * workspace's head have the bits of sat_yaapt_f32 (utt_dims == NULL) or sat_yaapt_ragged_f32, whatever chunk_frames is.
  *
+ * OVERLAP.  sat_yaapt_f32 serves frames of the time-domain stage that overlap their predecessor by at most 128 samples
+ * (plan->tda_len - plan->frame_jump <= 128).  The long form also accepts a larger overlap, at any frame count, as long as a frame overlaps at
+ * most 7 earlier frames:  plan->frame_jump < plan->tda_len <= 8 * plan->frame_jump  (and tda_len <= 1024 as before).  The reference's default
+ * options are such a plan: 560-sample frames at a hop of 160, three frames deep.  The reference subtracts each frame's mean in place on
+ * overlapping views of one buffer, so a sample loses the mean of every earlier frame that covers it, oldest first; for these plans the frame
+ * means and the NCCF run as a wide pair of kernels that does the same, sample by sample, every subtraction rounded.  A plan of a smaller
+ * overlap runs exactly the launches it ran before (the previous frame's mean only, also where tda_len > 2 * frame_jump).  A deeper plan is
+ * refused by name, with its depth, before anything is launched.
+ *
  * FRAMES.  4 frames up to the limit of the prefilter kernel, whose row offsets are 31-bit:  64 * plan->Lz * 4 < 2^31  and
  * 32 * plan->n * 4 < 2^31,  about 26 200 frames (8.7 minutes at a 20 ms hop).  A longer plan is refused by name before anything is launched.
  *
@@ -25,7 +34,8 @@
  * costs of the stage that runs, its median buffers, the compaction indices, the Viterbi's `pred` and `path` bytes.
  *
  * SAT_ERR_INVALID with a message, before anything is launched: a null pointer; every plan that sat_yaapt_f32 refuses for a reason other than
- * its frame count; fewer than 4 frames; a plan beyond the prefilter's limit; a chunk_frames outside its set.  SAT_ERR_WORKSPACE: a workspace
+ * its frame count or its overlap of more than 128 samples; a frame that overlaps more than 7 earlier ones; fewer than 4 frames; a plan beyond
+ * the prefilter's limit; a chunk_frames outside its set.  SAT_ERR_WORKSPACE: a workspace
  * smaller than sat_yaapt_long_workspace_bytes.
  */
 #ifndef SATOOLS_HIP_YAAPT_LONG_H

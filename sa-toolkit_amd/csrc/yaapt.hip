@@ -21,22 +21,6 @@
 
 namespace sat {
 
-// block-wide sum of one float per thread (256 threads), result broadcast; `red` = 8 floats of LDS
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  v = wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) red[threadIdx.x >> 6] = v;   // waves past the fourth (FFT helpers) only read
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max256(float v, float* red) {
-  v = wmax(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // ------------------------------------------------------------------------------------------------
 // prefilter: zero-pad, (square), low-pass biquad -> clamp -> high-pass biquad -> clamp   (yaapt.py:42-51).
 // torchaudio's lfilter order (third party, restated in oracle/biquad.py, order "torchaudio"):
@@ -645,108 +629,16 @@ __global__ void __launch_bounds__(256) yaapt_nccf_kernel(const float* __restrict
                                                         const float* __restrict__ spec, float* __restrict__ scal,
                                                         float* __restrict__ tp, float* __restrict__ tm,
                                                         int* __restrict__ status, const int* __restrict__ U, const Plan P) {
-  __shared__ float d[1024];
-  __shared__ float phi[1024];
-  __shared__ float red[8];
-  __shared__ int s_first;
-  const int tid = threadIdx.x;
-  const int k = blockIdx.x, sig = blockIdx.y, b = blockIdx.z;
-  const int nf = P.nframes;                       // row stride
-  if (k >= ulen(U, b, 2, nf)) return;
-  const size_t oidx = ((size_t)b * 2 + sig) * nf + k;
-  const float sp = spec[(size_t)b * nf + k];
-  const float pstd = scal[b * 4 + 0];
-  const float fthr = 5.0f * pstd;
-  const float rlo = tmax(sp - 2.0f * pstd, P.f0_min);
-  const float rhi = tmin(sp + 2.0f * pstd, P.f0_max);
-  const float fa = floorf(P.fs / rhi), fb = floorf(P.fs / rlo);
-  float pitch = 0.f, merit = 0.f;
-  const int n = P.tda_len;
-  if (!(fa != fa) && !(fb != fb)) {
-    const int lag_min = (int)fa - P.nccf_center;
-    const int lag_max = (int)fb + P.nccf_center;
-    const int N = n - lag_max;
-    // The reference walks the frames in order and ends at the first that fails: scal[1] keeps the smallest (frame, code), both
-    // signals of a frame have the same lags and so the same code; yaapt_refine_dp_kernel turns it into the utterance's status
-    if (N <= 0 || lag_min < 1) {
-      if (tid == 0) atomicMin((int*)scal + b * 4 + 1, k * 4 + 2);  // the reference asserts N > 0 (yaapt.py:586)
-    } else if (lag_max < lag_min) {
-      // the spectral pitch lies outside [f0_min, f0_max] by more than two deviations: the reference asks stride_matrix for
-      // lag_max - lag_min < 0 rows and fails (yaapt.py:594)
-      if (tid == 0) atomicMin((int*)scal + b * 4 + 1, k * 4 + 3);
-    } else {
-      const float* x = filt + ((size_t)b * 2 + sig) * P.Lz + (size_t)k * P.frame_jump;
-      const float* fm = fmean + ((size_t)b * 2 + sig) * nf;
-      const float mk = fm[k];
-      const float mprev = k > 0 ? fm[k - 1] : 0.f;
-      const int ov = P.tda_len - P.frame_jump;
-      for (int j = tid; j < n; j += 256) {
-        float v = x[j];
-        if (k > 0 && j < ov) v = v - mprev;
-        d[j] = v - mk;
-        phi[j] = 0.f;
-      }
-      __syncthreads();
-      float part = 0.f;
-      for (int j = tid; j < N; j += 256) part += d[j] * d[j];
-      const float pw = block_sum256(part, red);
-      const int nl = lag_max - lag_min;
-      for (int l = tid; l < nl; l += 256) {
-        const float* row = d + lag_min + l;
-        float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-        int j = 0;
-        for (; j + 4 <= N; j += 4) {
-          n0 = fmaf(row[j], d[j], n0); q0 = fmaf(row[j], row[j], q0);
-          n1 = fmaf(row[j + 1], d[j + 1], n1); q1 = fmaf(row[j + 1], row[j + 1], q1);
-          n2 = fmaf(row[j + 2], d[j + 2], n2); q2 = fmaf(row[j + 2], row[j + 2], q2);
-          n3 = fmaf(row[j + 3], d[j + 3], n3); q3 = fmaf(row[j + 3], row[j + 3], q3);
-        }
-        for (; j < N; ++j) { n0 = fmaf(row[j], d[j], n0); q0 = fmaf(row[j], row[j], q0); }
-        const float nume = (n0 + n1) + (n2 + n3);
-        const float den = (q0 + q1) + (q2 + q3);
-        phi[lag_min + l] = nume / sqrtf(den * pw + 0.0f);
-      }
-      __syncthreads();
-      // cmp_rate: first index with phi[n] > phi[n-1], > phi[n+1], > nccf_thresh1 inside [lag_min+c, lag_max-c]
-      const int c = P.nccf_center;
-      int first = 1 << 30;
-      float amax = 0.f;  // phi is zero outside the lag window
-      for (int i = tid; i < n; i += 256) {
-        const float v = phi[i];
-        amax = fmaxf(amax, v);   // NaN entries are skipped by fmaxf, like they never win a '>' test
-        if (i >= lag_min + c && i <= lag_max - c && v > phi[i - 1] && v > phi[i + 1] && v > P.nccf_thresh1)
-          first = min(first, i);
-      }
-      amax = block_max256(amax, red);
-      first = wmin_i(first);
-      if (tid == 0) s_first = 1 << 30;
-      __syncthreads();
-      if ((tid & 63) == 0) atomicMin(&s_first, first);
-      __syncthreads();
-      first = s_first;
-      if (first < (1 << 30)) {
-        bool take = amax > P.nccf_thresh2;
-        if (!take) {
-          const float v = phi[first];
-          take = true;  // argmax(phi[first-c : first+c+1]) == c
-          for (int i = first - c; i < first; ++i) take = take && (phi[i] < v);
-          for (int i = first + 1; i <= first + c; ++i) take = take && (phi[i] <= v);
-        }
-        if (take) {
-          pitch = (float)((double)P.fs / (double)(first + 1));
-          merit = phi[first];
-          if (merit > 1.0f) merit = merit / merit;
-        }
-      }
-    }
-  }
-  if (tid == 0) {
-    const float diff = fabsf(pitch - sp);
-    const float m1 = diff < fthr ? 1.f : 0.f;
-    const float match = (1.f - diff / fthr) * m1;
-    tp[oidx] = pitch;
-    tm[oidx] = (P.merit_boost1 * merit) * match;
-  }
+  // the first `ov` samples carry the previous frame's mean and no older one (an overlap of at most 128 samples: yaapt_check_plan; the
+  // wide form of csrc/yaapt_long/ subtracts every earlier mean).  The statements: yaapt_nccf_body.h, which the wide form includes too.
+#define YAAPT_NCCF_PREVIOUS_MEANS()             \
+  const float mprev = k > 0 ? fm[k - 1] : 0.f;  \
+  const int ov = P.tda_len - P.frame_jump
+#define YAAPT_NCCF_HEAD(v, j) \
+  if (k > 0 && j < ov) v = v - mprev
+#include "yaapt_nccf_body.h"
+#undef YAAPT_NCCF_HEAD
+#undef YAAPT_NCCF_PREVIOUS_MEANS
 }
 
 // refine + dynamic + path1 -> final pitch.  One wave per utterance; frames spread over lanes.
@@ -817,7 +709,9 @@ int yaapt_check_plan(const Plan& P, int B, bool resident) {
                   P.pk_min_lag - 0 >= 0, "yaapt: SHC range out of the 256-bin kernel window");
   SAT_REQUIRE(P.min_shc * (P.nharm + 1) + (P.max_shc - P.min_shc) * (P.nharm + 1) + P.wl <= 5 * 256,
               "yaapt: SHC harmonics exceed the spectral kernel's magnitude window");
-  SAT_REQUIRE(P.tda_len <= 1024 && P.tda_len > P.frame_jump && P.tda_len - P.frame_jump <= 128,
+  // the overlap of at most 128 samples is the resident kernels' (two head loads per lane, the previous mean only); the long form has
+  // kernels for a frame that overlaps several earlier ones and its own limit on their number
+  SAT_REQUIRE(P.tda_len <= 1024 && P.tda_len > P.frame_jump && (!resident || P.tda_len - P.frame_jump <= 128),
               "yaapt: tda_frame_length / frame_space combination not supported");
   SAT_REQUIRE(P.median_value >= 1 && P.median_value <= 7 && (P.median_value & 1), "yaapt: median_value must be odd <= 7");
   if (resident)

@@ -34,6 +34,21 @@ __device__ __forceinline__ int wmin_i(int v) {
   for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
   return v;
 }
+// block-wide sum of one float per thread (256 threads), result broadcast; `red` = 8 floats of LDS
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  v = wsum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) red[threadIdx.x >> 6] = v;   // waves past the fourth (FFT helpers) only read
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max256(float v, float* red) {
+  v = wmax(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
 
 // torch.maximum / torch.minimum propagate NaN
 __device__ __forceinline__ float tmax(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
@@ -170,7 +185,7 @@ struct YaaptBuffers {
 size_t yaapt_ws_floats(const Plan& P, int B);
 YaaptBuffers yaapt_carve(const Plan& P, int B, void* workspace);
 // every requirement of yaapt_run on a plan but the workspace's size; `resident` = with the 4..2048 frame range of the
-// one-block kernels (the long form has its own range)
+// one-block kernels and their overlap of at most 128 samples (the long form has its own ranges)
 int yaapt_check_plan(const Plan& P, int B, bool resident);
 // status memset, prefilter, staged twiddles, NLFER, energy norm, spectrum, peaks  /  NCCF: the per-frame kernels, any frame count
 int yaapt_launch_front(const Plan& P, const float* wav, const int32_t* U, int32_t* status, const float* hann, const float* kaiser,

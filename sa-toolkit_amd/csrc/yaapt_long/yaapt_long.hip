@@ -16,6 +16,8 @@
 // The arithmetic and its order are the resident kernels': float64 sums are lane-strided by 64 from frame 0 whatever CH is, the per-step
 // expressions of path1_long are those of path1_wave, so a plan of up to 2048 frames gives the resident form's bits.
 // Everything else (prefilter .. peaks, NCCF) is launched by csrc/yaapt.hip's own launchers: the same kernels.
+// A plan whose frames overlap by more than 128 samples (the reference's default options: 560-sample frames at a hop of 160) is served
+// here alone, at any length: the frame means and the NCCF then run as the wide pair further down.
 #include "../common.h"
 #include "../yaapt_dev.h"
 #include "../../../include/satools_hip_yaapt_long.h"
@@ -178,6 +180,113 @@ __global__ void __launch_bounds__(256) yaapt_long_frame_means_kernel(const float
   }
 }
 
+// ---- the wide pair: a frame that overlaps more than its predecessor (tda_len - frame_jump > 128, the reference's defaults among them) ----
+// time_track's frames are overlapping views of ONE buffer and crs_corr subtracts each frame's mean in place, so sample j of frame k
+// has lost the means of every earlier frame that covers it, oldest first, each subtraction rounded (n = tda_len, J = frame_jump):
+//     v = x[k J + j];   for i = D .. 1:  if (k - i >= 0 && j < n - i J) v = v - mean[k - i];      D = ceil(n / J) - 1
+//     mean[k] = mean_j(v);   d[j] = v - mean[k]
+// yaapt_long_frame_means_kernel is the case D = 1 with at most 128 overlapping samples.  Here the buffer itself is walked: the ring holds
+// the samples of the frame at hand that earlier frames have touched (its first ov = n - J samples, the part on the critical path) as the
+// reference's buffer holds them, and a step of the walk, mean[k] in hand, turns it into frame k + 1's head:
+//     in flight   positions (k + 1) J .. k J + ov     ring <- ring - mean[k]
+//     raw         positions max(..) .. k J + n        ring <- x - mean[k]        min(J, ov) <= 512 samples, loaded one frame ahead
+// and sums the new head on the way, so that  mean[k + 1] = (head sum + tail sum) / n  needs one wave reduction and no barrier: position p is
+// always handled by lane p & 63, a lane reads from the ring only what it stored there itself.  The recurrence-free tails (j >= ov) are
+// reduced a chunk ahead by all four waves, as in yaapt_long_frame_means_kernel.
+constexpr int YL_WIDE_DEPTH = 7;      // the earlier frames a frame may overlap: tda_len <= 8 frame_jump
+constexpr int YL_RING = 1024;         // >= tda_len
+constexpr int YL_RAW = 8;             // raw samples per lane that enter a head: min(frame_jump, ov) <= tda_len / 2 <= 512
+
+__device__ __forceinline__ int yl_own(int lo, int lane) { return lo + ((lane - lo) & 63); }   // the first position >= lo that `lane` handles
+
+__global__ void __launch_bounds__(256) yaapt_long_wide_frame_means_kernel(const float* __restrict__ filt, float* __restrict__ fmean,
+                                                                         const int* __restrict__ U, int CH, const Plan P) {
+  __shared__ float s_tail[YL_CHUNK_MAX];
+  __shared__ float s_ring[YL_RING];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x, sig = blockIdx.y;
+  if (!yl_row_fits(U, b, P)) return;
+  const float* x = filt + ((size_t)b * 2 + sig) * P.Lz;
+  float* m = fmean + ((size_t)b * 2 + sig) * P.nframes;
+  const int n = P.tda_len, J = P.frame_jump, ov = n - J;
+  const int nr = min(J, ov);
+  const int T = ulen(U, b, 3, P.tda_nframes);
+  // the raw samples of the step out of frame k: positions k J + n - nr .. k J + n, inside frame k; needed when there is a frame k + 1
+  auto raw = [&](int k, float* r) {
+    const int hi = k * J + n, p0 = yl_own(hi - nr, lane);
+#pragma unroll
+    for (int i = 0; i < YL_RAW; ++i) r[i] = (k + 1 < T && p0 + 64 * i < hi) ? x[p0 + 64 * i] : 0.f;
+  };
+  float cur[YL_RAW], nxt[YL_RAW];
+  float hsum = 0.f;                                    // the head sum of the frame to walk next
+  if (wave == 0) {
+    float part = 0.f;
+    for (int p = lane; p < ov; p += 64) {              // frame 0's head is untouched
+      const float v = x[p];
+      s_ring[p] = v;
+      part += v;
+    }
+    hsum = wsum(part);
+    raw(0, cur);
+  }
+  for (int c0 = 0; c0 < T; c0 += CH) {
+    const int nc = min(CH, T - c0);
+    __syncthreads();                                   // wave 0 has walked the previous chunk's tails
+    for (int k = c0 + wave; k < c0 + nc; k += 4) {
+      float part = 0.f;
+      for (int j = ov + lane; j < n; j += 64) part += x[(size_t)k * J + j];
+      part = wsum(part);
+      if (lane == 0) s_tail[k - c0] = part;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      for (int k = c0; k < c0 + nc; ++k) {
+        raw(k + 1, nxt);                               // prefetch
+        const float mean = (hsum + s_tail[k - c0]) / (float)n;
+        if (lane == 0) m[k] = mean;
+        float part = 0.f;
+        if (k + 1 < T) {
+          for (int p = yl_own((k + 1) * J, lane); p < k * J + ov; p += 64) {
+            const float v = s_ring[p & (YL_RING - 1)] - mean;
+            s_ring[p & (YL_RING - 1)] = v;
+            part += v;
+          }
+          const int hi = k * J + n, p0 = yl_own(hi - nr, lane);
+#pragma unroll
+          for (int i = 0; i < YL_RAW; ++i) {
+            if (p0 + 64 * i < hi) {
+              const float v = cur[i] - mean;
+              s_ring[(p0 + 64 * i) & (YL_RING - 1)] = v;
+              part += v;
+            }
+          }
+        }
+        hsum = wsum(part);
+#pragma unroll
+        for (int i = 0; i < YL_RAW; ++i) cur[i] = nxt[i];
+      }
+    }
+  }
+}
+
+// yaapt_nccf_kernel (csrc/yaapt.hip) with the frame rebuilt from every earlier mean that covers a sample, oldest first: the same statements
+__global__ void __launch_bounds__(256) yaapt_long_wide_nccf_kernel(const float* __restrict__ filt, const float* __restrict__ fmean,
+                                                                  const float* __restrict__ spec, float* __restrict__ scal,
+                                                                  float* __restrict__ tp, float* __restrict__ tm,
+                                                                  int* __restrict__ status, const int* __restrict__ U, const Plan P) {
+  // frame k - i covers the first n - i J samples of frame k (none from i = D + 1 on: the entry point holds D to YL_WIDE_DEPTH)
+#define YAAPT_NCCF_PREVIOUS_MEANS()                                            \
+  const int J = P.frame_jump;                                                  \
+  float mp[YL_WIDE_DEPTH];                                                     \
+  _Pragma("unroll") for (int i = 1; i <= YL_WIDE_DEPTH; ++i) mp[i - 1] = (k - i >= 0 && n - i * J > 0) ? fm[k - i] : 0.f
+#define YAAPT_NCCF_HEAD(v, j)                                                  \
+  _Pragma("unroll") for (int i = YL_WIDE_DEPTH; i >= 1; --i)                   \
+    if (k - i >= 0 && j < n - i * J) v = v - mp[i - 1]
+#include "../yaapt_nccf_body.h"
+#undef YAAPT_NCCF_HEAD
+#undef YAAPT_NCCF_PREVIOUS_MEANS
+}
+
 // LDS: floats sl[6][SP] so[6][SP] se[SP]; bytes s_pred[6][CH]
 __global__ void __launch_bounds__(64) yaapt_long_refine_dp_kernel(const float* __restrict__ tp, const float* __restrict__ tm,
                                                                  const float* __restrict__ spec, const float* __restrict__ energy,
@@ -232,6 +341,12 @@ extern "C" int sat_yaapt_long_f32(const sat_yaapt_plan* plan, const float* wav, 
   const int32_t* U = utt_dims;
   const int ok = yaapt_check_plan(P, B, false);
   if (ok != SAT_OK) return ok;
+  // frames that overlap more than their predecessor run the wide pair of kernels: up to YL_WIDE_DEPTH earlier frames
+  const int depth = P.frame_jump > 0 ? (P.tda_len + P.frame_jump - 1) / P.frame_jump - 1 : YL_WIDE_DEPTH + 1;
+  SAT_REQUIRE(depth <= YL_WIDE_DEPTH,"yaapt_long: tda_frame_length / frame_space combination not supported: a frame of %d samples at a "
+              "hop of %d overlaps %d earlier frames (depth %d), at most %d are supported (tda_len <= %d * frame_jump)", P.tda_len,
+              P.frame_jump, depth, depth, YL_WIDE_DEPTH, YL_WIDE_DEPTH + 1);
+  const bool wide = P.tda_len - P.frame_jump > 128;
   SAT_REQUIRE(P.nframes >= 4, "yaapt_long: %d frames not supported (4 frames at least)", P.nframes);
   // the prefilter kernel's buffer descriptors cover a block's 32 utterances (64 filtered rows) with 31-bit offsets; 32767 is what the
   // compaction's short frame indices take, far above it
@@ -259,10 +374,18 @@ extern "C" int sat_yaapt_long_f32(const sat_yaapt_plan* plan, const float* wav, 
   if (front != SAT_OK) return front;
   hipLaunchKernelGGL(yaapt_long_spec_post_kernel, dim3(B), dim3(64), post_lds, s, W.cand, W.spec, W.scal, status, U, arena, CH, P);
   SAT_LAUNCH_CHECK("yaapt_long_spec_post_kernel");
-  hipLaunchKernelGGL(yaapt_long_frame_means_kernel, dim3(B, 2), dim3(256), 0, s, W.filt, W.fmean, U, CH, P);
-  SAT_LAUNCH_CHECK("yaapt_long_frame_means_kernel");
-  const int nccf = yaapt_launch_nccf(P, U, status, W, B, s);
-  if (nccf != SAT_OK) return nccf;
+  if (wide) {
+    hipLaunchKernelGGL(yaapt_long_wide_frame_means_kernel, dim3(B, 2), dim3(256), 0, s, W.filt, W.fmean, U, CH, P);
+    SAT_LAUNCH_CHECK("yaapt_long_wide_frame_means_kernel");
+    hipLaunchKernelGGL(yaapt_long_wide_nccf_kernel, dim3(P.nframes, 2, B), dim3(256), 0, s, W.filt, W.fmean, W.spec, W.scal, W.tp, W.tm,
+                       status, U, P);
+    SAT_LAUNCH_CHECK("yaapt_long_wide_nccf_kernel");
+  } else {
+    hipLaunchKernelGGL(yaapt_long_frame_means_kernel, dim3(B, 2), dim3(256), 0, s, W.filt, W.fmean, U, CH, P);
+    SAT_LAUNCH_CHECK("yaapt_long_frame_means_kernel");
+    const int nccf = yaapt_launch_nccf(P, U, status, W, B, s);
+    if (nccf != SAT_OK) return nccf;
+  }
   hipLaunchKernelGGL(yaapt_long_refine_dp_kernel, dim3(B), dim3(64), dp_lds, s, W.tp, W.tm, W.spec, W.energy, W.vuv, f0, W.scal, status,
                      W.refined, U, arena, CH, P);
   SAT_LAUNCH_CHECK("yaapt_long_refine_dp_kernel");

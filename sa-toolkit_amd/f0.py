@@ -302,6 +302,20 @@ def plan_frames(n, opts):
     return len(range(half, n + 2 * pad - half, int(math.floor(g("frame_space") * sr / 1000))))
 
 
+MAX_RESIDENT_OVERLAP = 128      # sat_yaapt_f32 / sat_yaapt_ragged_f32: tda_len - frame_jump (yaapt_check_plan, csrc/yaapt.hip)
+LONG_MAX_DEPTH = 7              # sat_yaapt_long_f32: the earlier frames a frame may overlap, ceil(tda_len / frame_jump) - 1
+
+
+def plan_overlap(opts):
+    """tda_len - frame_jump of make_plan(n, opts) (no length enters) in plain Python, for the dispatch of `track` like `plan_frames`:
+    above MAX_RESIDENT_OVERLAP a frame of time_track overlaps more than the resident kernels subtract means for (the reference's own
+    defaults: 560 - 160 = 400) and the batch goes to the long form, which has kernels for it"""
+    g = lambda k: opts.get(k, DEFAULTS[k])
+    tda = opts["frame_lengtht"] if ("frame_lengtht" in opts and "tda_frame_length" not in opts) else g("tda_frame_length")
+    sr = g("sr")
+    return int(tda * sr / 1000) - int(math.floor(g("frame_space") * sr / 1000))
+
+
 def long_frames_ok(P):
     """whether sat_yaapt_long_f32 takes the plan's length: the prefilter kernel's 31-bit row offsets (about 26 200 frames at a 20 ms hop)"""
     return 32 * P.n * 4 < 2 ** 31 and 64 * P.Lz * 4 < 2 ** 31 and P.nframes <= 32767
@@ -311,7 +325,8 @@ def yaapt_long(wav, opts, lengths=None, chunk_frames=0, defer_status=False, retu
     """`yaapt` (lengths None) and `yaapt_ragged` in one function, for any frame count from 4 up to the prefilter's limit
     (sat_yaapt_long_f32): the per-utterance stages walk the frames in chunks of `chunk_frames` (0 = the default, else a multiple of 64 up to
     2048) instead of holding the utterance in one block's LDS.  Same arithmetic in the same order: up to 2048 frames the result has the bits
-    of `yaapt` / `yaapt_ragged`.  return_aux: also the named views of the workspace's head (`workspace_views`)."""
+    of `yaapt` / `yaapt_ragged`.  Also the only form for options whose frames overlap by more than 128 samples (up to LONG_MAX_DEPTH earlier
+    frames: the reference's defaults overlap three).  return_aux: also the named views of the workspace's head (`workspace_views`)."""
     if not wav.is_cuda:
         raise _lib.SatError("yaapt_long runs on the HIP device only (no CPU fallback); move the input to 'cuda'")
     if wav.dim() != 2:
@@ -366,8 +381,10 @@ def yaapt_long(wav, opts, lengths=None, chunk_frames=0, defer_status=False, retu
 def track(wav, opts, lengths=None, defer_status=False):
     """the F0 of a batch at any length the device takes: a batch plan of up to MAX_RESIDENT_FRAMES frames goes to `yaapt` (lengths None) or
     `yaapt_ragged` exactly as before, a longer one to `yaapt_long` (every row of a ragged batch then: the rows' results are the same
-    bits either way).  What Net.get_f0 / get_f0_ragged / convert / convert_padded and the batch job call."""
-    if plan_frames(wav.shape[-1], opts) <= MAX_RESIDENT_FRAMES:
+    bits either way).  Options whose frames overlap by more than MAX_RESIDENT_OVERLAP samples (the reference's defaults, a 10 ms hop) go to
+    `yaapt_long` at every length: its wide kernels alone serve them.
+    What Net.get_f0 / get_f0_ragged / convert / convert_padded and the batch job call."""
+    if plan_overlap(opts) <= MAX_RESIDENT_OVERLAP and plan_frames(wav.shape[-1], opts) <= MAX_RESIDENT_FRAMES:
         if lengths is None:
             return yaapt(wav, opts, defer_status=defer_status)
         return yaapt_ragged(wav, lengths, opts, defer_status=defer_status)
